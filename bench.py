@@ -3,7 +3,19 @@
 LLaVA-1.5-7B (bf16), search_width = 512.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gcg|joint|pgd|pgd_gcg|gemma_joint|opt125m]
-                    [--extra-workloads joint,pgd,gemma_joint | none]
+                    [--extra-workloads joint,pgd,gemma_joint | none] [--full] [--dump-outputs DIR]
+
+A plain run does what its headline figure needs and nothing more: build the model, W warm-up steps, the K timed
+steps (plus the one untimed step the pipelined step boundary needs behind them), the outputs if --dump-outputs is
+given, the JSON line.  Everything else described below -- the profiled steps behind `roofline` / `gemms` / `kernels`,
+the eager gradient-pass profile, the extra workloads, the CPU baseline, the detail file and, on several GPUs, the
+run's own one-GPU leg and `scaling_table` -- runs only with --full (an explicit --profile-steps, --extra-workloads or
+--detail still asks for its part alone).  In a plain run those fields of the line are null.
+
+--dump-outputs DIR writes what the headline workload's run hands its caller, as of its last timed step, in float64
+(float32 for the image): DIR/losses.npy (the step losses from step 0 through the last timed step), DIR/suffix_ids.npy
+(the token ids of the suffix that step chose) and, for PGD workloads, DIR/image.npy (the image after that step).
+Every input is seeded, so two builds given the same arguments can be compared output for output.
 
 A "step" is one full pass of the hot path: gradient pass -> (PGD projection) ->
 mask/top-k/scatter sampling -> retokenisation filter -> candidate splice + forward +
@@ -682,6 +694,8 @@ def measure(args, workload: str, steps: int, warmup: int, n_prof: int, device, w
     cfg = BimodalAttackConfig(num_steps=total, images_folder=tempfile.mkdtemp(prefix="bma_bench_"), **cfg_kw)
 
     marks = {}
+    dump = bool(primary and args.dump_outputs)
+    last = {}           # --dump-outputs: the newest PGD image (a reference, no copy inside the timed steps)
 
     def barrier_clock():
         if world > 1:
@@ -697,7 +711,8 @@ def measure(args, workload: str, steps: int, warmup: int, n_prof: int, device, w
         torch.cuda.synchronize(device)
 
     def hook(i: int) -> None:
-        log(f"{workload}: step {i}/{total}" + (" (profiled, outside the timed region)" if timed_end <= i < total else ""))
+        log(f"{workload}: step {i}/{total}" + ((" (profiled, outside the timed region)" if n_prof else " (untimed, behind the timed region)")
+                                               if timed_end <= i < total else ""))
         if i == warmup:
             for k_ in attack.score_stats:
                 attack.score_stats[k_] = 0
@@ -710,6 +725,8 @@ def measure(args, workload: str, steps: int, warmup: int, n_prof: int, device, w
                 marker()
             marks["stats"] = dict(attack.score_stats)
             marks["ids"] = attack._last["sampled"][:1].clone() if getattr(attack, "_last", None) else None
+            if dump and "image" in last:
+                marks["image"] = last["image"].detach().float().cpu().numpy()
             if n_prof:
                 native.profile_enable(True)      # event brackets cost a few us per launch: kept OUT of the timing (resets the tallies)
                 gemms.on = True
@@ -723,9 +740,24 @@ def measure(args, workload: str, steps: int, warmup: int, n_prof: int, device, w
     gemms = GemmTimer.for_model(model, attack.fused.qkv if attack.fused.enabled else [])
     gemms.rec = []
     attack.fused.gemm_probe = gemms
+    if dump and wl["pgd_attack"]:
+        pgd_step = attack.perform_pgd_step
+
+        def pgd_kept(*a, **kw):
+            last["image"] = pgd_step(*a, **kw)
+            return last["image"]
+        attack.perform_pgd_step = pgd_kept
     log(f"{workload}: engine constructed; running")
     res = attack.run(messages, goal, target, image)
     log(f"{workload}: run finished")
+    outputs = None
+    if dump:
+        import numpy as np
+        ids = tok(res.strings[timed_end - 1], add_special_tokens=False)["input_ids"]
+        outputs = {"losses": np.asarray(res.losses[:timed_end], dtype=np.float64),
+                   "suffix_ids": np.asarray(ids, dtype=np.float64).reshape(-1)}
+        if "image" in marks:
+            outputs["image"] = marks["image"]
     prof = native.profile_read()
     native.profile_enable(False)
 
@@ -923,7 +955,7 @@ def measure(args, workload: str, steps: int, warmup: int, n_prof: int, device, w
         out["projection"] = (f"what {emulate} GPUs WOULD print as `value` if every rank took this rank's time and the "
                              "collectives cost nothing: an upper bound from one process, not a measurement")
     keep = dict(model=model, tok=tok, proc=proc, messages=messages, goal=goal, target=target, image=image, norm=norm,
-                cfg_kw=cfg_kw, wl=wl, collectives=attack.shard.n_collectives, total_steps=total)
+                cfg_kw=cfg_kw, wl=wl, collectives=attack.shard.n_collectives, total_steps=total, outputs=outputs)
     del attack
     return out, keep
 
@@ -993,21 +1025,23 @@ _GUARD = None            # rank 0 of a multi-GPU run only
 TP_HUNG_STATUS = 4       # exit status of every rank when the tensor-parallel leg's watchdog fires
 
 
-def tp_ab(args, out: dict, device, world: int, rank: int) -> None:
+def tp_ab(args, out: dict, device, world: int, rank: int) -> "dict | None":
     """Several GPUs: the SAME timed block a second time (same seed, same steps, same model object) with the batch-1
     gradient pass TENSOR-PARALLEL over the ranks (EngineOptions.tp_gradient, as one hipGraph with its RCCL all-reduces
     inside on the nccl backend) instead of replicated on each -- the replicated pass is the serial term of a sharded step
      and the tensor-parallel one has never met xGMI, so the first multi-GPU run carries its own A/B.  The
     better leg becomes the headline (`value`, `ms_per_step`, phases, losses); both are reported under
     `rccl: {tp_off_ms, tp_on_ms, chosen}`.  The first leg's line is complete before the second starts: if the second
-    leg raises, or exceeds TP_LEG_LIMIT_S (a collective that never returns), the first leg's line is what is printed."""
+    leg raises, or exceeds TP_LEG_LIMIT_S (a collective that never returns), the first leg's line is what is printed.
+    Returns the tensor-parallel leg's --dump-outputs arrays when that leg became the headline, else None."""
     import threading
     import torch
     rc = out["rccl"]
     rc.update(tp_off_ms=out["ms_per_step"], tp_on_ms=None, chosen="off")
+    on_outputs = None
     if os.environ.get("BMA_BENCH_TP_AB", "1") in ("0", "false", "False"):
         rc["tp_note"] = "A/B skipped (BMA_BENCH_TP_AB=0)"
-        return
+        return on_outputs
     done = threading.Event()
 
     def watchdog():
@@ -1036,8 +1070,8 @@ def tp_ab(args, out: dict, device, world: int, rank: int) -> None:
     threading.Thread(target=watchdog, daemon=True).start()
     try:
         log("tensor-parallel gradient pass: the same timed block again (A/B against the replicated pass)")
-        on, _ = measure(args, args.workload, args.steps, args.warmup, 0, device, world, rank, primary=True,
-                        engine_kw=dict(tp_gradient="graph"))
+        on, on_keep = measure(args, args.workload, args.steps, args.warmup, 0, device, world, rank, primary=True,
+                              engine_kw=dict(tp_gradient="graph"))
         eng = on.get("engine") or {}
         rc["tp_on_ms"] = on["ms_per_step"]
         rc["tp_graph"] = "gradient_tp" in (eng.get("graphs_captured") or [])
@@ -1050,6 +1084,7 @@ def tp_ab(args, out: dict, device, world: int, rank: int) -> None:
                       "final_loss", "finite", "losses_timed", "engine", "forward_roofline", "gradient_pass_ms_each"):
                 out[k] = on.get(k)
             out["config"]["gradient_pass"] = "tensor-parallel over the ranks"
+            on_outputs = on_keep["outputs"]
             rc["tp_note"] = ("headline = the tensor-parallel leg; `roofline` and the per-kernel tables were taken in the replicated "
                              "leg's profiled steps (the scoring kernels are the same in both)")
     except Exception as e:              # the replicated leg's line stands on its own
@@ -1060,6 +1095,7 @@ def tp_ab(args, out: dict, device, world: int, rank: int) -> None:
             pass
     finally:
         done.set()
+    return on_outputs
 
 
 def scaling_table(dist, out: dict, solo, world: int) -> dict:
@@ -1086,6 +1122,22 @@ def scaling_table(dist, out: dict, solo, world: int) -> dict:
     return t
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(folder: str, outputs: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(folder, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(folder, f"{name}.npy"), a)
+    log(f"outputs of the last timed step written to {folder}: " + ", ".join(f"{n} {a.shape}" for n, a in outputs.items()))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1094,12 +1146,13 @@ def main() -> None:
     ap.add_argument("--workload", default="gcg", choices=sorted(WORKLOADS))
     ap.add_argument("--extra-workloads", default=None,
                     help="comma list of further workloads measured after --workload and reported under `workloads` "
-                         "(default: joint,pgd,gemma_joint when --workload gcg runs on one GPU; 'none' to skip)")
+                         "(default: joint,pgd,gemma_joint when --full and --workload gcg runs on one GPU; 'none' to skip)")
     ap.add_argument("--extra-steps", type=int, default=5, help="timed steps of each extra workload (2 warm-up steps)")
     ap.add_argument("--search-width", type=int, default=None)
     ap.add_argument("--layers", type=int, default=32, help="debug only: fewer layers is NOT the benchmark")
-    ap.add_argument("--profile-steps", type=int, default=2,
-                    help="extra steps AFTER the timed region with HIP-event brackets around kernels (rooflines)")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="extra steps AFTER the timed region with HIP-event brackets around kernels (rooflines); "
+                         "default 2 with --full, else 0")
     ap.add_argument("--no-gradient-profile", action="store_true", help="skip the eager per-GEMM profile of the gradient pass")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-width", type=int, default=32)
@@ -1108,7 +1161,14 @@ def main() -> None:
     ap.add_argument("--no-prefix-reuse", action="store_true")
     ap.add_argument("--detail", default=None, help="where the full result goes (default gpurun_out/bench_detail.json); "
                                                    "the stdout line is the short summary of it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: profiled steps, gradient-pass profile, extra workloads, CPU "
+                         "baseline, detail file, the own one-GPU leg of a multi-GPU run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the headline run's outputs as of its last timed step to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.profile_steps is None:
+        args.profile_steps = 2 if args.full else 0
     if args.steps is None:
         args.steps = 8 if args.workload == "opt125m" else 5
 
@@ -1155,7 +1215,7 @@ def main() -> None:
 
     n_prof = max(0, args.profile_steps)
     solo = None
-    if world > 1 and os.environ.get("BMA_BENCH_N1_LEG", "1") not in ("0", "false", "False"):
+    if world > 1 and args.full and os.environ.get("BMA_BENCH_N1_LEG", "1") not in ("0", "false", "False"):
         # The run's OWN one-GPU leg: every rank runs the whole job by itself (EngineOptions.shard=False: no collectives), a few
         # steps, before the sharded legs -- what `scaling_table.efficiency_vs_own_n1` divides by (same box, same build, same clock
         # state as the N-GPU legs; the driver's separate N = 1 run is another box hours apart).
@@ -1171,13 +1231,16 @@ def main() -> None:
                         engine_kw=dict(tp_gradient=False) if world > 1 else None)
     if world > 1:
         out["rccl"] = rccl_info(torch, dist, device, world, keep)
-        tp_ab(args, out, device, world, rank)
-        out["scaling_table"] = scaling_table(dist, out, solo, world)
+        on_outputs = tp_ab(args, out, device, world, rank)
+        if on_outputs is not None:
+            keep["outputs"] = on_outputs
+        if args.full:
+            out["scaling_table"] = scaling_table(dist, out, solo, world)
 
     # ---- the other single-GPU BASELINE configurations, on the same models, under `workloads` ----------
     if args.extra_workloads is None:
         emulating = int(os.environ.get("BMA_EMULATE_WORLD", "0") or 0) > 1
-        extra = ["joint", "pgd", "gemma_joint"] if (args.workload == "gcg" and world == 1 and args.layers == 32
+        extra = ["joint", "pgd", "gemma_joint"] if (args.full and args.workload == "gcg" and world == 1 and args.layers == 32
                                                      and args.search_width is None and not emulating) else []
     else:
         extra = [w for w in args.extra_workloads.split(",") if w and w != "none"]
@@ -1200,7 +1263,7 @@ def main() -> None:
                 torch.cuda.synchronize(device)
             log(f"workload {w} done")
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             _MODELS.clear()
             out["cpu_baseline"] = cpu_baseline(args, keep["wl"], keep["model"], keep["tok"], keep["proc"], keep["messages"],
@@ -1212,12 +1275,17 @@ def main() -> None:
         out["cpu_baseline"] = None
     status = 0
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, keep["outputs"])
         detail = args.detail or os.path.join(REPO, "gpurun_out", "bench_detail.json")
+        if not (args.full or args.detail):
+            detail = None
         try:
-            os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
-            with open(detail, "w") as fh:
-                json.dump(_strict(out), fh, indent=1)
-            log(f"full detail (per-GEMM tables, kernels, engine state, notes) written to {detail}")
+            if detail is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(detail)), exist_ok=True)
+                with open(detail, "w") as fh:
+                    json.dump(_strict(out), fh, indent=1)
+                log(f"full detail (per-GEMM tables, kernels, engine state, notes) written to {detail}")
         except OSError as e:
             log(f"detail file not written: {e}")
             detail = None

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 if [ "$PART" != "b" ]; then
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep smoke
 # the driver's own command line first: every single-GPU BASELINE config in one JSON line
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --detail "$D/bench_driver_detail.json" > "$D/bench_driver.json" 2> "$D/bench_driver.err"; echo "driver-rc=$?"
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full --detail "$D/bench_driver_detail.json" > "$D/bench_driver.json" 2> "$D/bench_driver.err"; echo "driver-rc=$?"
 for w in gcg joint pgd gemma_joint; do
   timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d "$D" -o gp_$w -- python3 tools/grad_pass_profile.py --workload $w > "$D/gp_$w.txt" 2>&1; tail -1 "$D/gp_$w.txt"
   python3 tools/trace_by_grid.py "$D/gp_${w}_kernel_trace.csv" "$D/gp_${w}_by_grid.txt" 40 --between-markers; rm -f "$D/gp_${w}_kernel_trace.csv"
@@ -24,18 +24,18 @@ timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv 
 fi
 if [ "$PART" = "a" ]; then exit 0; fi
 for w in gcg joint pgd gemma_joint; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o kt_$w -- python3 bench.py --workload $w --no-cpu-baseline --extra-workloads none --detail "$D/bench_${w}_under_rocprof_detail.json" > "$D/bench_${w}_under_rocprof.json" 2> /dev/null; echo "kt-$w-rc=$?"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$D" -o kt_$w -- python3 bench.py --full --workload $w --no-cpu-baseline --extra-workloads none --detail "$D/bench_${w}_under_rocprof_detail.json" > "$D/bench_${w}_under_rocprof.json" 2> /dev/null; echo "kt-$w-rc=$?"
   python3 tools/trace_by_grid.py "$D/kt_${w}_kernel_trace.csv" "$D/kt_${w}_by_grid.txt" 70 --between-markers
 done
 rm -f "$D"/*_kernel_trace.csv
-timeout -k 10 300 python bench.py --workload pgd_gcg --no-cpu-baseline --extra-workloads none --detail "$D/bench_pgd_gcg_detail.json" > "$D/bench_pgd_gcg.json" 2> /dev/null; echo "pgd_gcg-rc=$?"
+timeout -k 10 300 python bench.py --full --workload pgd_gcg --no-cpu-baseline --extra-workloads none --detail "$D/bench_pgd_gcg_detail.json" > "$D/bench_pgd_gcg.json" 2> /dev/null; echo "pgd_gcg-rc=$?"
 for n in 2 4 8; do
-  BMA_EMULATE_WORLD=$n timeout -k 10 300 python bench.py --no-cpu-baseline --detail "$D/bench_em${n}_detail.json" > "$D/bench_em$n.json" 2> /dev/null; echo "em$n-rc=$?"
+  BMA_EMULATE_WORLD=$n timeout -k 10 300 python bench.py --full --no-cpu-baseline --detail "$D/bench_em${n}_detail.json" > "$D/bench_em$n.json" 2> /dev/null; echo "em$n-rc=$?"
 done
 for n in 2 4 8; do
-  BMA_EMULATE_WORLD=$n timeout -k 10 300 python bench.py --workload joint --no-cpu-baseline --detail "$D/bench_joint_em${n}_detail.json" > "$D/bench_joint_em$n.json" 2> /dev/null; echo "joint-em$n-rc=$?"
+  BMA_EMULATE_WORLD=$n timeout -k 10 300 python bench.py --full --workload joint --no-cpu-baseline --detail "$D/bench_joint_em${n}_detail.json" > "$D/bench_joint_em$n.json" 2> /dev/null; echo "joint-em$n-rc=$?"
 done
-timeout -k 10 300 python bench.py --workload opt125m --detail "$D/bench_opt125m_detail.json" > "$D/bench_opt125m.json" 2> "$D/bench_opt125m.err"; echo "opt125m-rc=$?"
+timeout -k 10 300 python bench.py --full --workload opt125m --detail "$D/bench_opt125m_detail.json" > "$D/bench_opt125m.json" 2> "$D/bench_opt125m.err"; echo "opt125m-rc=$?"
 timeout -k 10 200 python tools/gemm_bench.py --rows 65,44 --json "$D/gemm_bench.json" 2>&1 | grep -v amdgpu.ids > "$D/gemm_bench.txt"; echo "gemm-bench-rc=$?"
 timeout -k 10 200 python tools/gemm_bench.py --chain --rows 65,44 --json "$D/gemm_chain.json" 2>&1 | grep -v amdgpu.ids > "$D/gemm_chain.txt"; echo "gemm-chain-rc=$?"
 timeout -k 10 200 python tools/gemm_bench.py --mid --rows 644,599 --json "$D/gemm_mid_bench.json" 2>&1 | grep -v amdgpu.ids > "$D/gemm_mid_bench.txt"; echo "gemm-mid-bench-rc=$?"

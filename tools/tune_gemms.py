@@ -37,7 +37,7 @@ def main():
             # candidate dealing produces, not those of a smaller search width
             print(f"== tuning {wl} as rank 0 of {world}", flush=True)
             r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", wl, "--steps", "1", "--warmup", "1",
-                                "--no-cpu-baseline"], env=dict(env, BMA_EMULATE_WORLD=str(world)), cwd=REPO)
+                                "--no-cpu-baseline", "--full"], env=dict(env, BMA_EMULATE_WORLD=str(world)), cwd=REPO)
             if r.returncode != 0:
                 print(f"   (failed with {r.returncode}; continuing)", flush=True)
     if not sys.argv[1:] or "gcg" in workloads:
