@@ -250,6 +250,7 @@ class _RunState:
         self.image_original: Optional[Tensor] = None
         self.pending = None                    # a gradient pass computed / queued for the NEXT step: (gradients, seconds, span)
         self.fuse_pgd = False
+        self.apgd = None                       # pgd_rule "apgd": ops.ApgdState of this run (fresh per run, reference :1337)
         self.trace = None
         self.writer = None
         self.losses: List[float] = []
@@ -627,6 +628,49 @@ class BimodalAttack:
         out = ops.linf_step(x.contiguous(), image_grad.to(torch.float32).contiguous(),
                             image_original.detach().contiguous(), eps, alpha)
         return out.requires_grad_()
+
+    def perform_autopgd_step(self, image: Tensor, eps: float, image_grad: Tensor, image_original: Tensor,
+                             current_loss: Optional[float], iter_idx: int, state: "ops.ApgdState") -> Tensor:
+        """The reference's second update rule (:1039-1110): momentum step of eta = 2*eps, halved with a restart from the
+        best image when a checkpoint (every 10 steps) finds too few improvements.  `state` holds what the reference keeps
+        on `self` between calls; one launch of bma_apgd_step per call, its flags decided on the host."""
+        x = image.detach()
+        if x.dtype != torch.float32:
+            raise TypeError("the PGD image must be float32 (the reference feeds ToTensor() output)")
+        out = state.step(x.contiguous(), image_grad.to(torch.float32).contiguous(), image_original.detach().contiguous(),
+                         current_loss, iter_idx)
+        return out.requires_grad_()
+
+    def _pgd_update(self, rs: "_RunState", sp: "_StepState") -> Tensor:
+        """The step's image update by EngineOptions.pgd_rule.  The reference's `current_loss` (:421, :612) is the loss
+        of the previous step, already on the host in every mode."""
+        cfg = self.config
+        if self.opt.pgd_rule != "apgd":
+            return self.perform_pgd_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original)
+        if rs.apgd is None:
+            rs.apgd = ops.ApgdState(cfg.eps)
+        a = rs.apgd
+        cur = rs.losses[-1] if rs.losses else None
+        if sp.st is not None:
+            if a.prev is None:
+                sp.st["apgd_x0"] = rs.image_original.detach().cpu().numpy()
+            x_in = rs.image.detach().cpu().numpy()
+            prev_in = x_in if a.prev is None else a.prev.cpu().numpy()
+            best_in = x_in if a.best is None else a.best.cpu().numpy()
+        out = self.perform_autopgd_step(rs.image, cfg.eps, sp.g_img, rs.image_original, cur, sp.i, a)
+        if sp.st is not None:
+            eta, take_best, restart = a.last
+            sp.st["apgd"] = dict(current_loss=cur, eta=eta, take_best=take_best, restart=restart, eta_next=a.eta,
+                                 count=a.count, best_loss=a.best_loss, last_best=a.last_best, x=x_in,
+                                 g=sp.g_img.to(torch.float32).cpu().numpy(), prev_in=prev_in, best_in=best_in,
+                                 prev_out=a.prev.cpu().numpy(), best_out=a.best.cpu().numpy())
+        return out
+
+    def _apgd_adopt(self, rs: "_RunState") -> None:
+        """Several ranks: rank 0's image has just overwritten this rank's (dist.sync_state); the APGD state that the step
+        derived from its own output follows it, so every rank's state stays rank 0's (no collective of its own)."""
+        if rs.apgd is not None and self.shard.enabled and self.shard.rank != 0:
+            rs.apgd.adopt(rs.image)
 
     # ------------------------------------------------------------ sampling
     def _width(self, step: int) -> int:
@@ -1369,6 +1413,7 @@ class BimodalAttack:
                 rs.writer.close()
 
         self.final_image = rs.image
+        self.apgd_state = rs.apgd                # pgd_rule "apgd": the rule's state after the last step (None otherwise)
         k = rs.losses.index(min(rs.losses))
         return BimodalAttackResult(
             best_loss=rs.losses[k], best_string=rs.strings[k], losses=rs.losses, strings=rs.strings,
@@ -1412,11 +1457,11 @@ class BimodalAttack:
             return
         if sp.span is not None:           # gradient_ahead: timed on the stream, read after the step
             sp.pgd_span = _Span()
-            rs.image = self.perform_pgd_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original)
+            rs.image = self._pgd_update(rs, sp)
             sp.pgd_span.stop()
         else:
             t0 = self._sync()
-            rs.image = self.perform_pgd_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original)
+            rs.image = self._pgd_update(rs, sp)
             sp.pgd_time = self._sync() - t0
             rs.t_pgd.append(sp.pgd_time)
         if sp.st is not None:
@@ -1427,6 +1472,7 @@ class BimodalAttack:
             # in-place overwrite behind it (the packed broadcast of the sampling phase) would leave the
             # winner re-score and the next token gradient on the pre-sync pixels
             self.shard.sync_state(rs.image)
+            self._apgd_adopt(rs)
             sp.image_synced = True
             # only the token gradient of this pass is used (the image has just been stepped)
             (sp.g_tok, sp.g_img, _), sp.grad_time = self._grad_pass(rs, sp, tokens_only=True)
@@ -1443,6 +1489,7 @@ class BimodalAttack:
             early = self._early if (self._early is not None and self._early["step"] == i) else None
             t_s = time.perf_counter()
             sp.sampled_all, sp.job = self.candidate_sampling(i, rs.optim_ids, sp.g_tok, image if cfg.pgd_attack else None)
+            self._apgd_adopt(rs)
             # (the sampling kernels' own ~0.3 ms of GPU time are booked with the scoring phase: event pairs
             # around them, recorded while the gradient graph was still running, read 3-18 ms too long)
             sp.flying = (sp.span, time.perf_counter() - t_s, sp.pgd_span)
@@ -1454,6 +1501,8 @@ class BimodalAttack:
             t0 = self._sync()
             sp.sampled_all, sp.job = self.candidate_sampling(i, rs.optim_ids, sp.g_tok,
                                                              image if (cfg.pgd_attack and not sp.image_synced) else None)
+            if not sp.image_synced:
+                self._apgd_adopt(rs)
             if cfg.gcg_attack:
                 sp.samp_time = self._sync() - t0
         if self._filter_first_now():

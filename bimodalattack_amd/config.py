@@ -75,7 +75,7 @@ class EngineOptions:
     """Knobs of the MI355X engine that the reference has no field for: the ones a test or bench.py flips.
 
     Read from keyword arguments of :func:`bimodalattack_amd.run` or from the environment (``BMA_<NAME>``), never from
-    ``BimodalAttackConfig``.  Every one of them only changes speed (tests/test_attack_gpu.py runs the reference's golden
+    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule`` only changes speed (tests/test_attack_gpu.py runs the reference's golden
     trajectories with each restructuring off).  Finer switches that exist for A/B measurements only are module constants
     read from the environment once (round 5: 42 options -> 27): ``ops.OWN_KERNELS`` (each hand-written batch-1 kernel),
     ``attack.MASKLESS_B1_ATTENTION`` / ``CHUNK_QUANTUM`` / ``EMULATE_WORLD``, ``fused.FUSE_QK_ROPE``,
@@ -177,6 +177,11 @@ class EngineOptions:
     # Round per-candidate losses to the model dtype before the argmin, as the reference's model-dtype cross-entropy does
     # ("quirks").
     loss_in_model_dtype: bool = True
+    # The image update of every PGD step: "linf" = the reference's perform_pgd_step (:1030-1037, sign step of
+    # alpha*eps); "apgd" = its perform_autopgd_step (:1039-1110, momentum, eta = 2*eps halved at checkpoints with a
+    # restart from the best image; config.alpha is not used), which the reference ships with its call sites commented out.
+    # The one option that changes results: opt-in, never a default.
+    pgd_rule: str = "linf"
 
     _BOOLS = ("prefix_reuse", "target_rows_only", "graph_gradient", "graph_scoring", "fused_elementwise", "derived_weight_copies",
               "own_b1_kernels", "grad_prefix_reuse", "fuse_add_norm", "joint_winner_from_batch", "shared_prefix_attention",
@@ -223,6 +228,8 @@ class EngineOptions:
             opts.tp_gradient = "graph" if env["BMA_TP_GRADIENT"] == "graph" else env["BMA_TP_GRADIENT"] not in off
         if "BMA_CHUNK" in env:
             opts.chunk = int(env["BMA_CHUNK"])
+        if "BMA_PGD_RULE" in env:
+            opts.pgd_rule = env["BMA_PGD_RULE"]
         for k, v in overrides.items():
             if v is None:
                 continue
@@ -233,6 +240,8 @@ class EngineOptions:
             setattr(opts, k, v)
         if opts.rng_device not in ("model", "cpu"):
             raise ValueError(f"rng_device must be 'model' or 'cpu', got {opts.rng_device!r}")
+        if opts.pgd_rule not in ("linf", "apgd"):
+            raise ValueError(f"pgd_rule must be 'linf' or 'apgd', got {opts.pgd_rule!r}")
         if opts.tp_gradient not in (False, True, "graph"):
             raise ValueError(f"tp_gradient must be False, True or 'graph', got {opts.tp_gradient!r}")
         return opts

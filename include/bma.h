@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BMA_VERSION 112 /* 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
+#define BMA_VERSION 113 /* 0.1.13: bma_apgd_step (the reference's auto-PGD image update, opt-in); 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
 
 /* element types of model-dtype tensors */
 enum { BMA_F32 = 0, BMA_BF16 = 1, BMA_F16 = 2 };
@@ -57,6 +57,24 @@ const char* bma_strerror(int code);
  * ------------------------------------------------------------------------- */
 int bma_linf_step(const float* x, const float* g, const float* x0, int64_t n,
                   float eps, float step, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * a5b  perform_autopgd_step  (:1039-1110), the per-pixel part of one call:
+ *   z    = clamp(max(min(x - eta*sign(g), x0+eps), x0-eps), 0, 1)
+ *   new  = clamp(max(min((x + 0.75*(z-x)) + 0.25*(x-prev), x0+eps), x0-eps), 0, 1)
+ *   prev = x;  take_best: best = new;  restart: out = prev = best;  else out = new
+ * fp32, each operation rounded as the reference's torch ops round it (no FMA);
+ * min / max propagate NaN from either operand and return the first on a tie.
+ * eta, the losses and the counters live on the host: take_best (the step loss
+ * beat the best one) and restart (a checkpoint halved eta) are 0 or 1.  With
+ * restart=1, take_best=0 only best is read.
+ * Aliasing: out may alias x (in place).  prev and best are the caller's state
+ * buffers: distinct from each other and from x, g, x0 and out (BMA_EINVAL).
+ * Pointers 4-byte aligned; the 16-byte vector path is used when all six are
+ * 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+int bma_apgd_step(const float* x, const float* g, const float* x0, float* prev, float* best, int64_t n,
+                  float eps, float eta, int take_best, int restart, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------
  * a2  cross-entropy over the target slice
@@ -433,7 +451,7 @@ enum {
   BMA_K_TOPK = 3, BMA_K_SCATTER = 4, BMA_K_SPLICE = 5,
   BMA_K_CE_ROWS_B1 = 6 /* B == 1: the gradient pass */, BMA_K_RMSNORM = 7, BMA_K_SWIGLU = 8,
   BMA_K_ROPE = 9, BMA_K_ATTN_MERGE = 10, BMA_K_GATHER_ROWS = 11,
-  BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_COUNT = 19
+  BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_APGD = 19, BMA_K_COUNT = 20
 };
 int bma_profile_enable(int on);
 int bma_profile_read(int kernel, int64_t* launches, double* total_ms, double* total_bytes);

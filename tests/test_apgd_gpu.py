@@ -1,0 +1,358 @@
+"""The auto-PGD image update on the MI355X: bma_apgd_step against the reference's own calls (g8_apgd_unit) and the
+float32 restatement of test_apgd.py, and whole runs with ``pgd_rule="apgd"`` against the reference's trajectories
+(g8_*), checked in two layers as test_attack_gpu.check_against_golden checks the default rule."""
+
+import json
+import os
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from test_apgd import apgd_restated, same_bits, unit_calls
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+with open(os.path.join(GOLDEN, "g8_meta.json")) as _f:
+    META8 = json.load(_f)["cases"]
+with open(os.path.join(GOLDEN, "g5_meta.json")) as _f:
+    META5 = json.load(_f)["cases"]
+
+
+# ------------------------------------------------------------------ the kernel
+@pytest.mark.parametrize("in_place", [False, True])
+def test_kernel_equals_the_reference_calls(in_place):
+    from bimodalattack_amd import ops
+    z, calls = unit_calls()
+    x0 = torch.from_numpy(z["x0"]).to(DEV)
+    eps = float(z["eps"])
+    prev = best = None
+    for i, cur, x, g, rec in calls:
+        xd = torch.from_numpy(x).to(DEV)
+        if prev is None:
+            prev, best = xd.clone(), xd.clone()
+        out = ops.apgd_step(xd, torch.from_numpy(g).to(DEV), x0, prev, best, eps, float(rec["eta_used"]),
+                            bool(rec["take_best"]), bool(rec["restart"]), out=xd if in_place else None)
+        assert (out.data_ptr() == xd.data_ptr()) == in_place
+        got = out.cpu().numpy()
+        assert same_bits(got, rec["out"]), f"call {i}: output"
+        assert same_bits(prev.cpu().numpy(), rec["prev"]), f"call {i}: prev"
+        assert same_bits(best.cpu().numpy(), rec["best"]), f"call {i}: best"
+
+
+@pytest.mark.parametrize("n,offset", [(3 * 336 * 336, 0), (3 * 896 * 896, 0), (4097, 0), (4099, 0), (1023, 1), (5, 1), (3, 0)])
+def test_kernel_equals_the_restatement_at_every_size(n, offset):
+    """LLaVA's and Gemma-3's image sizes, tails of 1 and 3 behind the float4 body, and views one float off the 16-byte
+    grid (the scalar kernel alone) -- every combination of the two flags."""
+    from bimodalattack_amd import ops
+    rs = np.random.RandomState(n)
+    eps = 64 / 255
+    x0 = rs.uniform(0, 1, n).astype(np.float32)
+    x = np.clip(x0 + rs.uniform(-eps, eps, n).astype(np.float32), 0, 1).astype(np.float32)
+    prev = np.clip(x0 + rs.uniform(-eps, eps, n).astype(np.float32), 0, 1).astype(np.float32)
+    best = rs.uniform(0, 1, n).astype(np.float32)
+    g = rs.standard_normal(n).astype(np.float32)
+    g[rs.choice(n, min(n, 7), replace=False)] = [np.nan, 0.0, -0.0, np.inf, -np.inf, 1e-30, -1e-30][:min(n, 7)]
+
+    def dev(a):
+        buf = torch.empty(a.size + offset, dtype=torch.float32, device=DEV)
+        v = buf[offset:]
+        v.copy_(torch.from_numpy(a))
+        return v
+
+    for take_best in (False, True):
+        for restart in (False, True):
+            p, b = dev(prev), dev(best)
+            out = ops.apgd_step(dev(x), dev(g), dev(x0), p, b, eps, 2 * eps, take_best, restart)
+            want = apgd_restated(x, g, x0, prev, best, eps, 2 * eps, take_best, restart)
+            for got, w, what in zip((out, p, b), want, ("out", "prev", "best")):
+                assert same_bits(got.cpu().numpy(), w), (n, offset, take_best, restart, what)
+    torch.cuda.synchronize()
+
+
+def test_kernel_refuses_aliased_state():
+    from bimodalattack_amd import ops
+    x = torch.rand(64, device=DEV)
+    p = x.clone()
+    with pytest.raises(ValueError):
+        ops.apgd_step(x, x, x, p, p, 0.1, 0.2, False, False)
+    with pytest.raises(ValueError):
+        ops.apgd_step(x, x, x, x, p.clone(), 0.1, 0.2, False, False)
+
+
+# ------------------------------------------------------------------ whole runs
+def run_g8(name, cfg_over=None, trace=True, meta=None, **engine):
+    from bimodalattack_amd import BimodalAttackConfig, run, synthetic as S
+    m = (meta or META8)[name]
+    model, tok, proc, image = S.tiny_case(m["kind"], device=DEV)
+    tmp = tempfile.mkdtemp(prefix="bma_apgd_")
+    cfg = BimodalAttackConfig(seed=1, verbosity="ERROR", optim_str_init=m["optim_str_init"], images_folder=tmp,
+                              **dict(m["config"], **(cfg_over or {})))
+    tr = [] if trace else None
+    engine.setdefault("strict", True)
+    engine.setdefault("pgd_rule", "apgd")
+    res = run(model, tok, proc, m["goal"], m["goal"], m["target"], image, cfg,
+              normalize=S.Normalize(S.CLIP_MEAN, S.CLIP_STD), rng_device="cpu", trace=tr, **engine)
+    return m, res, tr, tmp
+
+
+def check_in_situ(trace, res, eps):
+    """Layer 1, always exact: every step's kernel output and state equal the restatement applied to the engine's OWN
+    recorded inputs, and the host's flags equal the reference's logic applied to the engine's OWN losses."""
+    x0 = trace[0]["apgd_x0"]
+    eta, best_loss, last_best, count = 2 * eps, None, None, 0
+    for i, st in enumerate(trace):
+        a = st["apgd"]
+        cur = res.losses[i - 1] if i else None
+        assert a["current_loss"] == cur, i
+        if i == 0:
+            best_loss = cur if cur is not None else float("inf")
+            last_best = best_loss
+        take_best = restart = False
+        used = eta
+        if cur is not None:
+            if cur < best_loss:
+                best_loss, take_best = cur, True
+            if cur < last_best:
+                count += 1
+            if (i + 1) % 10 == 0:
+                if count / 10 < 0.75 or best_loss == last_best:
+                    eta, restart = eta / 2, True
+                count, last_best = 0, best_loss
+        assert (a["eta"], a["take_best"], a["restart"], a["eta_next"], a["count"], a["best_loss"]) == \
+            (used, take_best, restart, eta, count, best_loss), f"step {i}: host flags"
+        out, prev, best = apgd_restated(a["x"], a["g"], x0, a["prev_in"], a["best_in"], eps, a["eta"], take_best, restart)
+        assert same_bits(st["image_after_pgd"], out), f"step {i}: kernel output vs restatement"
+        assert same_bits(a["prev_out"], prev) and same_bits(a["best_out"], best), f"step {i}: state vs restatement"
+        if i:
+            assert same_bits(a["x"], trace[i - 1]["image_after_pgd"]), f"step {i}: input is the last output"
+
+
+# Bounds against the reference's image.  Under the default rule a device-vs-CPU rounding difference can flip the sign of
+# an (almost) zero pixel gradient (test_attack_gpu: at most 0.5 % of pixels per step).  Here too, the first step whose
+# image differs at all may differ in at most 0.5 % of its pixels.  From that step on the two runs score DIFFERENT images:
+# a flipped pixel stays different (the momentum term carries x - prev forward, eta = 2*eps moves it across the whole box),
+# and the next gradients differ with it.  Measured on the tiny Gemma-3 case: 1 pixel of 9408 at step 17, 65 at step 18
+# (0.69 %), 1 again after the restart at step 19; losses 1e-3 apart.  So after the first differing pixel the images are
+# held to 2 % and the losses to rtol 1e-2; before it, losses to rtol 1e-4 as for the default rule.
+FIRST_PIXELS, LATER_PIXELS, LATER_RTOL = 0.005, 0.02, 1e-2
+
+_AUDIT = {}
+
+
+def check_against_g8(name, m, res, trace):
+    """Layer 2: the reference's trajectory, within the bounds above.  The comparison stops (escape hatch, as for the
+    token near-tie of check_against_golden) at the first step whose input suffix differs from the golden's -- a
+    near-tied candidate won -- or whose checkpoint decision differs while the deciding losses are tied within the
+    tolerance.  Returns (step it stopped at or None, first step whose image differed or None)."""
+    z = np.load(os.path.join(GOLDEN, f"g8_{name}.npz"))
+    assert len(trace) == m["steps"]
+    px_at = None
+    for i, st in enumerate(trace):
+        a = st["apgd"]
+        if not np.array_equal(st["optim_ids_in"], z[f"s{i}_optim_ids_in"]):
+            return i, px_at
+        if a["restart"] != bool(z[f"s{i}_restart"]):
+            bl, cur = float(z[f"s{i}_best_loss"]), a["current_loss"]
+            assert cur is not None and abs(cur - bl) <= 1e-4 * abs(bl) + 1e-6, f"step {i}: checkpoint decision differs"
+            return i, px_at
+        assert a["eta"] == float(z[f"s{i}_eta_used"]), f"step {i}: eta"
+        want, got = z[f"s{i}_image_after_pgd"], st["image_after_pgd"]
+        diff = ~((got == want) | (np.isnan(got) & np.isnan(want)))
+        if px_at is None and diff.any():
+            px_at = i
+            assert diff.mean() <= FIRST_PIXELS, f"step {i}: {diff.sum()} pixels differ"
+        assert diff.mean() <= LATER_PIXELS, f"step {i}: {diff.sum()} pixels differ"
+        rtol = 1e-4 if px_at is None else LATER_RTOL
+        for j, l in enumerate(st["losses"]):
+            np.testing.assert_allclose(l, z[f"s{i}_loss{j}"], rtol=rtol)
+        np.testing.assert_allclose(res.losses[i], z["losses"][i], rtol=rtol)
+    assert res.strings == m["strings"] and res.best_string == m["best_string"]
+    np.testing.assert_allclose(res.best_loss, float(z["best_loss"]), rtol=1e-4 if px_at is None else LATER_RTOL)
+    return None, px_at
+
+
+@pytest.mark.parametrize("name", sorted(META8))
+def test_apgd_trajectory_matches_reference(name):
+    m, res, trace, tmp = run_g8(name)
+    check_in_situ(trace, res, m["config"]["eps"])
+    assert any(st["apgd"]["restart"] for st in trace), "no restart: the case no longer reaches a halving"
+    assert sorted(os.listdir(tmp)) == sorted(f"{i}.png" for i in range(m["steps"]))      # save_images
+    _AUDIT[name] = check_against_g8(name, m, res, trace)
+
+
+def test_apgd_trajectories_audit():
+    """How many auto-PGD trajectories were held to the reference to their last step (runs behind the parametrised test)."""
+    if len(_AUDIT) < len(META8):
+        pytest.skip("the auto-PGD trajectories were not all run in this session")
+    ended = {k: v[0] for k, v in _AUDIT.items() if v[0] is not None}
+    pixels = {k: v[1] for k, v in _AUDIT.items() if v[1] is not None}
+    line = (f"auto-PGD trajectories compared to their last step: {len(_AUDIT) - len(ended)} of {len(_AUDIT)}; "
+            f"stopped early at: {ended}; first differing pixel (losses to rtol {LATER_RTOL} from there) at: {pixels}")
+    print(line)
+    import warnings
+    import conftest
+    conftest.AUDIT_LINES.append(line)
+    warnings.warn("golden audit: " + line, UserWarning, stacklevel=2)
+    assert len(_AUDIT) - len(ended) >= 3, ended
+
+
+@pytest.mark.parametrize("engine", [dict(gradient_ahead=False), dict(joint_winner_from_batch=False),
+                                    dict(fuse_pgd_only=False)])
+def test_apgd_routes_agree(engine):
+    """The plain route and the gradient-ahead / winner-from-batch route of joint mode, and PGD-only with and without the
+    fused loop, run the same rule: in situ exact, and the same losses as the default route."""
+    name = "llava_pgd" if "fuse_pgd_only" in engine else "llava_joint"
+    over = dict(num_steps=12)
+    m, base, _, _ = run_g8(name, over, trace=False)
+    m, res, trace, _ = run_g8(name, over, **engine)
+    check_in_situ(trace, res, m["config"]["eps"])
+    np.testing.assert_allclose(res.losses, base.losses, rtol=1e-5)
+    assert res.strings == base.strings
+
+
+def test_apgd_with_early_stop():
+    """early_stop keeps the plain loop (and stops on a match); the rule runs unchanged up to there."""
+    m, res, trace, _ = run_g8("llava_pgd_gcg", dict(num_steps=12, early_stop=True))
+    check_in_situ(trace, res, m["config"]["eps"])
+    assert len(res.losses) == len(trace)
+
+
+def test_linf_given_explicitly_is_the_default_bit_for_bit():
+    a = run_g8("llava_pgd", meta=META5, trace=False, pgd_rule=None)
+    from bimodalattack_amd import synthetic as S  # noqa: F401
+    b = run_g8("llava_pgd", meta=META5, trace=False, pgd_rule="linf")
+    assert a[1].losses == b[1].losses and a[1].strings == b[1].strings
+    # the images the run wrote are the same bytes
+    for i in range(a[0]["steps"]):
+        assert open(os.path.join(a[3], f"{i}.png"), "rb").read() == open(os.path.join(b[3], f"{i}.png"), "rb").read()
+
+
+def test_apgd_in_a_gcg_only_run_changes_nothing():
+    a = run_g8("llava_gcg", meta=META5, trace=False, pgd_rule="linf")
+    b = run_g8("llava_gcg", meta=META5, trace=False, pgd_rule="apgd")
+    assert a[1].losses == b[1].losses and a[1].strings == b[1].strings
+
+
+class _HostReads:
+    """Counts host synchronisations and device-to-host reads while a block runs."""
+
+    NAMES = (("torch.cuda", "synchronize"), ("Tensor", "item"), ("Tensor", "cpu"), ("Tensor", "tolist"))
+
+    def __enter__(self):
+        self.n = 0
+        self._orig = []
+        for owner, attr in self.NAMES:
+            obj = torch.cuda if owner == "torch.cuda" else torch.Tensor
+            fn = getattr(obj, attr)
+            self._orig.append((obj, attr, fn))
+
+            def wrap(*a, _fn=fn, **k):
+                self.n += 1
+                return _fn(*a, **k)
+            setattr(obj, attr, wrap)
+        return self
+
+    def __exit__(self, *exc):
+        for obj, attr, fn in self._orig:
+            setattr(obj, attr, fn)
+
+
+@pytest.mark.parametrize("name", ["llava_pgd", "llava_joint", "llava_pgd_gcg"])
+def test_apgd_adds_no_host_reads(name):
+    counts = {}
+    for rule in ("linf", "apgd"):
+        # (filter_first pinned: its automatic choice reads the host at steps that depend on the candidates, which the two
+        # rules' different images change)
+        run_g8(name, dict(num_steps=3), trace=False, pgd_rule=rule, save_images=False, filter_first=False)   # warm
+        with _HostReads() as h:
+            run_g8(name, dict(num_steps=12), trace=False, pgd_rule=rule, save_images=False, filter_first=False)
+        counts[rule] = h.n
+    assert counts["apgd"] == counts["linf"], counts
+
+
+# ------------------------------------------------------------------ two ranks on one GPU
+def _apgd_rank_worker(rank, world, port, name, out):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        torch.cuda.set_device(0)
+        out.put((rank,) + _run_with_state(name))
+    finally:
+        dist.destroy_process_group()
+
+
+def _run_with_state(name):
+    from bimodalattack_amd import BimodalAttackConfig, synthetic as S
+    from bimodalattack_amd.attack import BimodalAttack
+    from bimodalattack_amd.config import EngineOptions
+    m = META8[name]
+    model, tok, proc, image = S.tiny_case(m["kind"], device=DEV)
+    cfg = BimodalAttackConfig(seed=1, verbosity="ERROR", optim_str_init=m["optim_str_init"], images_folder=tempfile.mkdtemp(),
+                              **m["config"])
+    atk = BimodalAttack(model, tok, proc, cfg, S.Normalize(S.CLIP_MEAN, S.CLIP_STD),
+                        EngineOptions.from_env(rng_device="cpu", strict=True, pgd_rule="apgd"))
+    res = atk.run(m["goal"], m["goal"], m["target"], image)
+    a = atk.apgd_state
+    return (res.losses, res.strings, atk.final_image.detach().cpu().numpy(), a.prev.cpu().numpy(), a.best.cpu().numpy(),
+            (a.eta, a.best_loss, a.last_best, a.count))
+
+
+@pytest.mark.parametrize("name", ["llava_joint", "llava_pgd_gcg", "llava_pgd"])
+def test_apgd_two_ranks_equal_single(name):
+    import socket
+    import torch.multiprocessing as mp
+    single = _run_with_state(name)
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ctx = mp.get_context("spawn")
+    out = ctx.Queue()
+    procs = [ctx.Process(target=_apgd_rank_worker, args=(r, 2, port, name, out)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = [out.get(timeout=300) for _ in procs]
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    for rank, losses, strings, img, prev, best, scalars in got:
+        assert strings == single[1], rank
+        np.testing.assert_allclose(losses, single[0], rtol=1e-5)
+        assert scalars == single[5], rank
+        for x, y in ((img, single[2]), (prev, single[3]), (best, single[4])):
+            assert same_bits(x, y), rank
+    r0, r1 = sorted(got, key=lambda t: t[0])
+    assert r0[1:3] == r1[1:3] and r0[6] == r1[6]
+    assert all(same_bits(x, y) for x, y in zip(r0[3:6], r1[3:6]))
+
+
+# ------------------------------------------------------------------ full size
+def test_7b_apgd_pgd_only_steps():
+    """12 PGD-only steps of the synthetic LLaVA-1.5-7B (BASELINE configs[1]'s eps) with the auto-PGD rule: in situ exact,
+    finite losses, no fast path given up."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from bench import build_plugins
+    from bimodalattack_amd import BimodalAttackConfig
+    from bimodalattack_amd.attack import BimodalAttack
+    from bimodalattack_amd.config import EngineOptions
+
+    dev = torch.device(DEV)
+    steps, eps = 12, 64 / 255
+    model, tok, proc, messages, goal, target, image, norm = build_plugins("pgd", dev, torch.bfloat16, 32)
+    cfg = BimodalAttackConfig(num_steps=steps, search_width=8, seed=1, verbosity="ERROR", pgd_attack=True, gcg_attack=False,
+                              eps=eps, alpha=4 / 255, images_folder=tempfile.mkdtemp())
+    trace = []
+    atk = BimodalAttack(model, tok, proc, cfg, norm,
+                        EngineOptions.from_env(save_images=False, strict=True, pgd_rule="apgd", trace=trace))
+    res = atk.run(messages, goal, target, image.detach().clone())
+    assert not atk.engine_state()["fallbacks"], atk.engine_state()["fallbacks"]
+    assert np.isfinite(res.losses).all() and len(res.losses) == steps
+    check_in_situ(trace, res, eps)
+    x = atk.final_image.detach()
+    assert float((x - image.detach()).abs().max()) <= eps + 1e-6 and float(x.min()) >= 0 and float(x.max()) <= 1
+    print(f"7B auto-PGD, {steps} steps: losses {np.round(res.losses, 4).tolist()}")

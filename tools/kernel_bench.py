@@ -62,6 +62,13 @@ def cases():
         gr = torch.randn(n, generator=g, device=DEV)
         return lambda: ops.linf_step(x, gr, x0, 64 / 255, 4 / 255, out=x)
 
+    def apgd(n):
+        # the steady-state call (no improvement, no checkpoint): 16 B read + 8 B written per pixel
+        x0 = torch.rand(n, generator=g, device=DEV)
+        x, prev, best = x0.clone(), x0.clone(), x0.clone()
+        gr = torch.randn(n, generator=g, device=DEV)
+        return lambda: ops.apgd_step(x, gr, x0, prev, best, 64 / 255, 2 * 64 / 255, False, False, out=x)
+
     def scatter(B, n_opt=19, k=256):
         ids = torch.randint(0, 32000, (n_opt,), generator=g, device=DEV)
         tk = torch.randint(0, 32000, (n_opt, k), generator=g, device=DEV)
@@ -295,6 +302,8 @@ def cases():
         "mask_topk/llava_19x32064_f32": ("mask_topk", lambda: topk(19, 32064, dtype=torch.float32)),
         "linf/llava_3x336x336": ("linf", lambda: linf(3 * 336 * 336)),
         "linf/gemma_3x896x896": ("linf", lambda: linf(3 * 896 * 896)),
+        "apgd/llava_3x336x336": ("apgd", lambda: apgd(3 * 336 * 336)),
+        "apgd/gemma_3x896x896": ("apgd", lambda: apgd(3 * 896 * 896)),
         "sample_scatter/B512": ("sample_scatter", lambda: scatter(512)),
         # round 3: residual add + norm in one pass, the row list straight from the segments, the skinny weight-streaming product
         "rope/c3r_qk_N17152_H32_Dh128": ("rope", lambda: rope_qk(17152, 32, 32, 128)),
