@@ -251,6 +251,7 @@ class _RunState:
         self.pending = None                    # a gradient pass computed / queued for the NEXT step: (gradients, seconds, span)
         self.fuse_pgd = False
         self.apgd = None                       # pgd_rule "apgd": ops.ApgdState of this run (fresh per run, reference :1337)
+        self.l2 = None                         # pgd_norm "l2", plain rule: ops.L2Scratch of this run (workspace + norms)
         self.trace = None
         self.writer = None
         self.losses: List[float] = []
@@ -629,6 +630,17 @@ class BimodalAttack:
                             image_original.detach().contiguous(), eps, alpha)
         return out.requires_grad_()
 
+    def perform_l2_step(self, image: Tensor, eps: float, alpha: float, image_grad: Tensor, image_original: Tensor,
+                        scratch: "ops.L2Scratch") -> Tensor:
+        """x <- P(x - alpha*eps * g/||g||), P onto the L2 ball of radius eps around x0 and into [0, 1] (pgd_norm "l2";
+        the reference has no such update): three launches of bma_l2_step, the norms stay on the device."""
+        x = image.detach()
+        if x.dtype != torch.float32:
+            raise TypeError("the PGD image must be float32 (the reference feeds ToTensor() output)")
+        out = ops.l2_step(x.contiguous(), image_grad.to(torch.float32).contiguous(),
+                          image_original.detach().contiguous(), eps, alpha, scratch=scratch)
+        return out.requires_grad_()
+
     def perform_autopgd_step(self, image: Tensor, eps: float, image_grad: Tensor, image_original: Tensor,
                              current_loss: Optional[float], iter_idx: int, state: "ops.ApgdState") -> Tensor:
         """The reference's second update rule (:1039-1110): momentum step of eta = 2*eps, halved with a restart from the
@@ -642,13 +654,26 @@ class BimodalAttack:
         return out.requires_grad_()
 
     def _pgd_update(self, rs: "_RunState", sp: "_StepState") -> Tensor:
-        """The step's image update by EngineOptions.pgd_rule.  The reference's `current_loss` (:421, :612) is the loss
-        of the previous step, already on the host in every mode."""
+        """The step's image update by (EngineOptions.pgd_rule, pgd_norm).  The reference's `current_loss` (:421, :612) is
+        the loss of the previous step, already on the host in every mode."""
         cfg = self.config
+        l2 = self.opt.pgd_norm == "l2"
         if self.opt.pgd_rule != "apgd":
-            return self.perform_pgd_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original)
+            if not l2:
+                return self.perform_pgd_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original)
+            if rs.l2 is None:
+                rs.l2 = ops.L2Scratch(rs.image.device, rs.image.numel())
+                if sp.st is not None:
+                    sp.st["l2_x0"] = rs.image_original.detach().cpu().numpy()
+            if sp.st is not None:
+                x_in = rs.image.detach().cpu().numpy()
+            out = self.perform_l2_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original, rs.l2)
+            if sp.st is not None:
+                sp.st["l2"] = dict(x=x_in, g=sp.g_img.to(torch.float32).cpu().numpy(), out=out.detach().cpu().numpy(),
+                                   norms=rs.l2.norms.cpu().numpy())
+            return out
         if rs.apgd is None:
-            rs.apgd = ops.ApgdState(cfg.eps)
+            rs.apgd = ops.ApgdState(cfg.eps, "l2" if l2 else "linf")
         a = rs.apgd
         cur = rs.losses[-1] if rs.losses else None
         if sp.st is not None:
@@ -664,6 +689,8 @@ class BimodalAttack:
                                  count=a.count, best_loss=a.best_loss, last_best=a.last_best, x=x_in,
                                  g=sp.g_img.to(torch.float32).cpu().numpy(), prev_in=prev_in, best_in=best_in,
                                  prev_out=a.prev.cpu().numpy(), best_out=a.best.cpu().numpy())
+            if l2:
+                sp.st["apgd"].update(norm="l2", out=out.detach().cpu().numpy(), norms=a.scratch.norms.cpu().numpy())
         return out
 
     def _apgd_adopt(self, rs: "_RunState") -> None:
@@ -1414,6 +1441,7 @@ class BimodalAttack:
 
         self.final_image = rs.image
         self.apgd_state = rs.apgd                # pgd_rule "apgd": the rule's state after the last step (None otherwise)
+        self.l2_scratch = rs.l2 if rs.apgd is None else rs.apgd.scratch   # pgd_norm "l2": the last step's norms (None otherwise)
         k = rs.losses.index(min(rs.losses))
         return BimodalAttackResult(
             best_loss=rs.losses[k], best_string=rs.strings[k], losses=rs.losses, strings=rs.strings,

@@ -75,7 +75,7 @@ class EngineOptions:
     """Knobs of the MI355X engine that the reference has no field for: the ones a test or bench.py flips.
 
     Read from keyword arguments of :func:`bimodalattack_amd.run` or from the environment (``BMA_<NAME>``), never from
-    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule`` only changes speed (tests/test_attack_gpu.py runs the reference's golden
+    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule`` and ``pgd_norm`` only changes speed (tests/test_attack_gpu.py runs the reference's golden
     trajectories with each restructuring off).  Finer switches that exist for A/B measurements only are module constants
     read from the environment once (round 5: 42 options -> 27): ``ops.OWN_KERNELS`` (each hand-written batch-1 kernel),
     ``attack.MASKLESS_B1_ATTENTION`` / ``CHUNK_QUANTUM`` / ``EMULATE_WORLD``, ``fused.FUSE_QK_ROPE``,
@@ -182,6 +182,11 @@ class EngineOptions:
     # restart from the best image; config.alpha is not used), which the reference ships with its call sites commented out.
     # The one option that changes results: opt-in, never a default.
     pgd_rule: str = "linf"
+    # The threat model of that update: "linf" = the box |x - x0| <= eps of both reference rules; "l2" = the ball
+    # ||x - x0||_2 <= eps (eps in pixel units of the [0,1] image; csrc/l2_step.hip, contract in include/bma.h), which the
+    # reference does not have.  Orthogonal to pgd_rule: ("linf", "l2") is plain L2 PGD with a step of alpha*eps along
+    # g/||g||, ("apgd", "l2") is auto-PGD in the ball.  Changes results like pgd_rule: opt-in, never a default.
+    pgd_norm: str = "linf"
 
     _BOOLS = ("prefix_reuse", "target_rows_only", "graph_gradient", "graph_scoring", "fused_elementwise", "derived_weight_copies",
               "own_b1_kernels", "grad_prefix_reuse", "fuse_add_norm", "joint_winner_from_batch", "shared_prefix_attention",
@@ -230,6 +235,8 @@ class EngineOptions:
             opts.chunk = int(env["BMA_CHUNK"])
         if "BMA_PGD_RULE" in env:
             opts.pgd_rule = env["BMA_PGD_RULE"]
+        if "BMA_PGD_NORM" in env:
+            opts.pgd_norm = env["BMA_PGD_NORM"]
         for k, v in overrides.items():
             if v is None:
                 continue
@@ -242,6 +249,8 @@ class EngineOptions:
             raise ValueError(f"rng_device must be 'model' or 'cpu', got {opts.rng_device!r}")
         if opts.pgd_rule not in ("linf", "apgd"):
             raise ValueError(f"pgd_rule must be 'linf' or 'apgd', got {opts.pgd_rule!r}")
+        if opts.pgd_norm not in ("linf", "l2"):
+            raise ValueError(f"pgd_norm must be 'linf' or 'l2', got {opts.pgd_norm!r}")
         if opts.tp_gradient not in (False, True, "graph"):
             raise ValueError(f"tp_gradient must be False, True or 'graph', got {opts.tp_gradient!r}")
         return opts

@@ -128,6 +128,7 @@ extern "C" const char* bma_profile_kernel_name(int kernel) {
     case BMA_K_GEMM_MID: return "gemm_mid_kernel";
     case BMA_K_CAUSAL_ATTN: return "causal_attn_kernel";
     case BMA_K_APGD: return "apgd_step_vec4";
+    case BMA_K_L2: return "l2_step_passes";
     default: return "?";
   }
 }

@@ -95,6 +95,68 @@ def apgd_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, prev: torch.Te
     return out
 
 
+class L2Scratch:
+    """What the L2 entry points need beside the images, allocated ONCE per run: the fp64 partials of the norms (`ws`,
+    bma_l2_ws_bytes) and the three fp32 norms the latest call left behind (`norms`: ||g||, ||(x - step*u) - x0||, auto-PGD
+    also ||m - x0||; NaN until a call has written them).  Nothing in a run reads `norms` on the host."""
+
+    def __init__(self, dev: torch.device, n: int):
+        self.n = n
+        self.ws = torch.empty(max(1, lib.bma_l2_ws_bytes(n) // 8), dtype=torch.float64, device=dev)
+        self.norms = torch.full((3,), float("nan"), dtype=torch.float32, device=dev)
+
+
+def _l2_scratch(scratch: Optional[L2Scratch], x: torch.Tensor) -> L2Scratch:
+    if scratch is None:
+        return L2Scratch(x.device, x.numel())
+    if scratch.ws.device != x.device or scratch.n < x.numel():
+        raise ValueError("the L2 scratch belongs to another device or a smaller image")
+    return scratch
+
+
+def l2_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
+            out: Optional[torch.Tensor] = None, scratch: Optional[L2Scratch] = None) -> torch.Tensor:
+    """Plain PGD in the L2 ball of radius eps around x0 (include/bma.h, a5c): P(x - (alpha*eps) * g/(||g|| + 1e-10)),
+    P = scale back onto the ball, then clamp to [0, 1].  `scratch.norms` holds the call's norms afterwards."""
+    dev = _need_gpu(x, g, x0)
+    for t in (x, g, x0):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != x.shape:
+            raise ValueError("l2_step wants three contiguous float32 tensors of one shape")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != dev:
+        raise ValueError("bad out tensor")
+    scratch = _l2_scratch(scratch, x)
+    step = float(alpha * eps)  # the product of the two Python floats, as linf_step
+    check("bma_l2_step", lib.bma_l2_step(x.data_ptr(), g.data_ptr(), x0.data_ptr(), x.numel(), float(eps), step,
+                                         out.data_ptr(), scratch.ws.data_ptr(), scratch.norms.data_ptr(), _stream(dev)))
+    return out
+
+
+def apgd_l2_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, prev: torch.Tensor, best: torch.Tensor, eps: float,
+                 eta: float, take_best: bool, restart: bool, out: Optional[torch.Tensor] = None,
+                 scratch: Optional[L2Scratch] = None) -> torch.Tensor:
+    """The per-pixel part of one auto-PGD call in the L2 ball (include/bma.h, a5c): flags, state and aliasing rules of
+    `apgd_step`, the box replaced by the ball."""
+    dev = _need_gpu(x, g, x0, prev, best)
+    for t in (x, g, x0, prev, best):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != x.shape:
+            raise ValueError("apgd_l2_step wants five contiguous float32 tensors of one shape")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != dev:
+        raise ValueError("bad out tensor")
+    ptrs = {t.data_ptr() for t in (x, out)}
+    if prev.data_ptr() == best.data_ptr() or ptrs & {prev.data_ptr(), best.data_ptr()}:
+        raise ValueError("apgd_l2_step: prev and best are state buffers of their own (only out may alias x)")
+    scratch = _l2_scratch(scratch, x)
+    check("bma_apgd_l2_step", lib.bma_apgd_l2_step(x.data_ptr(), g.data_ptr(), x0.data_ptr(), prev.data_ptr(),
+                                                   best.data_ptr(), x.numel(), float(eps), float(eta),
+                                                   int(bool(take_best)), int(bool(restart)), out.data_ptr(),
+                                                   scratch.ws.data_ptr(), scratch.norms.data_ptr(), _stream(dev)))
+    return out
+
+
 class ApgdState:
     """What the reference's perform_autopgd_step keeps between calls (:1052-1061), for ONE run: eta, the best loss, the
     loss at the last checkpoint and the improvement count as Python floats / ints (as the reference keeps them), and the
@@ -103,8 +165,12 @@ class ApgdState:
 
     MOMENTUM, RHO, INTERVAL = 0.75, 0.75, 10
 
-    def __init__(self, eps: float):
+    def __init__(self, eps: float, norm: str = "linf"):
+        if norm not in ("linf", "l2"):
+            raise ValueError(f"ApgdState: norm must be 'linf' or 'l2', got {norm!r}")
         self.eps = eps
+        self.norm = norm                      # "l2": the ball instead of the box (bma_apgd_l2_step); decide() is the same
+        self.scratch: Optional[L2Scratch] = None
         self.started = False
         self.eta = 2 * eps                    # initial step size (:1058); config.alpha is not used
         self.best_loss = float("inf")
@@ -141,6 +207,10 @@ class ApgdState:
         if self.prev is None:
             self.prev, self.best = x.clone(), x.clone()
         eta, take_best, restart = self.decide(current_loss, i)
+        if self.norm == "l2":
+            if self.scratch is None:
+                self.scratch = L2Scratch(x.device, x.numel())
+            return apgd_l2_step(x, g, x0, self.prev, self.best, self.eps, eta, take_best, restart, scratch=self.scratch)
         return apgd_step(x, g, x0, self.prev, self.best, self.eps, eta, take_best, restart)
 
     def adopt(self, image: torch.Tensor) -> None:

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BMA_VERSION 113 /* 0.1.13: bma_apgd_step (the reference's auto-PGD image update, opt-in); 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
+#define BMA_VERSION 114 /* 0.1.14: bma_l2_step, bma_apgd_l2_step, bma_l2_ws_bytes (the PGD image update in the L2 ball, opt-in); 0.1.13: bma_apgd_step (the reference's auto-PGD image update, opt-in); 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
 
 /* element types of model-dtype tensors */
 enum { BMA_F32 = 0, BMA_BF16 = 1, BMA_F16 = 2 };
@@ -75,6 +75,46 @@ int bma_linf_step(const float* x, const float* g, const float* x0, int64_t n,
  * ------------------------------------------------------------------------- */
 int bma_apgd_step(const float* x, const float* g, const float* x0, float* prev, float* best, int64_t n,
                   float eps, float eta, int take_best, int restart, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * a5c  the PGD image update in the L2 ball (opt-in, EngineOptions.pgd_norm =
+ *      "l2"; the reference has no L2 update, this is the engine's own contract)
+ *
+ * All pixel arithmetic is fp32, rounded operation by operation (no FMA, IEEE
+ * division).  Norms are accumulated in fp64 and rounded once:
+ *   nrm(v) = float( sqrt( sum_i double(v_i)^2 ) )
+ * so the value does not depend on the order of summation beyond fp64 rounding
+ * (about 3e-10 relative at 2.4 M pixels; fp32 rounding boundaries are 6e-8
+ * apart).  The order is fixed all the same: two calls on one input are
+ * bitwise equal, there are no floating-point atomics.
+ *   P(y)  = clamp01( x0 + (y - x0) * f ),   f = min(eps / nrm(y - x0), 1.0f)
+ *           (a zero norm gives inf, so f = 1; NaN propagates through f and
+ *           through clamp01, which is compare+select)
+ *   u     = g / (nrm(g) + 1e-10f)
+ * bma_l2_step:       out = P(x - step*u)              multiply, then subtract
+ * bma_apgd_l2_step:  z   = P(x - eta*u)
+ *                    m   = (x + 0.75f*(z - x)) + 0.25f*(x - prev)
+ *                    new = P(m)
+ *                    prev = x;  take_best: best = new;  restart: out = prev =
+ *                    best;  else out = new -- flags, state and aliasing rules
+ *                    exactly as bma_apgd_step, including: with restart=1,
+ *                    take_best=0 only best is read (and norms is not written).
+ * eps is the L2 radius in pixel units of the [0,1] image.
+ * ws:    bma_l2_ws_bytes(n) bytes of scratch, 8-byte aligned (one fp64 partial
+ *        per workgroup and norm).  The call is a chain of 3 (plain) or 4
+ *        (auto-PGD) ordinary launches on `stream`; nothing waits inside a launch.
+ * norms: 3 floats the call leaves filled: [0] nrm(g), [1] nrm((x - step*u) - x0),
+ *        auto-PGD also [2] nrm(m - x0).  For tests and traces (later launches
+ *        of the same call read them back on the device; the host never does).
+ * Aliasing: out may alias x.  Pointers 4-byte aligned; the 16-byte vector path
+ * is used when all image pointers are 16-byte aligned.
+ * ------------------------------------------------------------------------- */
+size_t bma_l2_ws_bytes(int64_t n);
+int bma_l2_step(const float* x, const float* g, const float* x0, int64_t n, float eps, float step,
+                float* out, void* ws, float* norms, void* stream);
+int bma_apgd_l2_step(const float* x, const float* g, const float* x0, float* prev, float* best, int64_t n,
+                     float eps, float eta, int take_best, int restart, float* out, void* ws, float* norms,
+                     void* stream);
 
 /* ---------------------------------------------------------------------------
  * a2  cross-entropy over the target slice
@@ -451,7 +491,7 @@ enum {
   BMA_K_TOPK = 3, BMA_K_SCATTER = 4, BMA_K_SPLICE = 5,
   BMA_K_CE_ROWS_B1 = 6 /* B == 1: the gradient pass */, BMA_K_RMSNORM = 7, BMA_K_SWIGLU = 8,
   BMA_K_ROPE = 9, BMA_K_ATTN_MERGE = 10, BMA_K_GATHER_ROWS = 11,
-  BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_APGD = 19, BMA_K_COUNT = 20
+  BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_APGD = 19, BMA_K_L2 = 20 /* every pass of bma_l2_step / bma_apgd_l2_step */, BMA_K_COUNT = 21
 };
 int bma_profile_enable(int on);
 int bma_profile_read(int kernel, int64_t* launches, double* total_ms, double* total_bytes);

@@ -69,6 +69,22 @@ def cases():
         gr = torch.randn(n, generator=g, device=DEV)
         return lambda: ops.apgd_step(x, gr, x0, prev, best, 64 / 255, 2 * 64 / 255, False, False, out=x)
 
+    def l2(n):
+        # three passes (4 + 12 + 16 B per pixel); the figures printed are per PASS (launch), a call is launches / iters of them
+        x0 = torch.rand(n, generator=g, device=DEV)
+        x = x0.clone()
+        gr = torch.randn(n, generator=g, device=DEV)
+        sc = ops.L2Scratch(torch.device(DEV), n)
+        return lambda: ops.l2_step(x, gr, x0, 16.0, 0.125, out=x, scratch=sc)
+
+    def apgd_l2(n):
+        # the steady-state call (no improvement, no checkpoint): four passes (4 + 12 + 16 + 24 B per pixel)
+        x0 = torch.rand(n, generator=g, device=DEV)
+        x, prev, best = x0.clone(), x0.clone(), x0.clone()
+        gr = torch.randn(n, generator=g, device=DEV)
+        sc = ops.L2Scratch(torch.device(DEV), n)
+        return lambda: ops.apgd_l2_step(x, gr, x0, prev, best, 16.0, 32.0, False, False, out=x, scratch=sc)
+
     def scatter(B, n_opt=19, k=256):
         ids = torch.randint(0, 32000, (n_opt,), generator=g, device=DEV)
         tk = torch.randint(0, 32000, (n_opt, k), generator=g, device=DEV)
@@ -304,6 +320,10 @@ def cases():
         "linf/gemma_3x896x896": ("linf", lambda: linf(3 * 896 * 896)),
         "apgd/llava_3x336x336": ("apgd", lambda: apgd(3 * 336 * 336)),
         "apgd/gemma_3x896x896": ("apgd", lambda: apgd(3 * 896 * 896)),
+        "l2/llava_3x336x336": ("l2", lambda: l2(3 * 336 * 336)),
+        "l2/gemma_3x896x896": ("l2", lambda: l2(3 * 896 * 896)),
+        "apgd_l2/llava_3x336x336": ("l2", lambda: apgd_l2(3 * 336 * 336)),
+        "apgd_l2/gemma_3x896x896": ("l2", lambda: apgd_l2(3 * 896 * 896)),
         "sample_scatter/B512": ("sample_scatter", lambda: scatter(512)),
         # round 3: residual add + norm in one pass, the row list straight from the segments, the skinny weight-streaming product
         "rope/c3r_qk_N17152_H32_Dh128": ("rope", lambda: rope_qk(17152, 32, 32, 128)),
@@ -431,6 +451,10 @@ def main():
             tf = gf / 1e3 / (us * 1e-6)
             results[name].update(algorithmic_GFLOP=gf, achieved_TFLOPs=tf, frac_of_2500TFLOPs=tf / 2500.0)
             extra = f"  {gf:6.1f} GFLOP {tf:6.0f} TFLOP/s = {tf / 2500.0:4.2f} of the MFMA peak"
+        if kid == "l2":                       # a call is a chain of launches: the sum of its passes beside the per-pass mean
+            passes = p["launches"] // max(1, args.iters)
+            results[name].update(passes_per_call=passes, call_us=us * passes, call_MB=mb * passes)
+            extra = f"  per pass; x{passes} = {us * passes:.1f} us, {mb * passes:.2f} MB per call"
         print(f"{name:40s} {us:9.1f} us  {mb:9.2f} MB  {gbs:8.0f} GB/s  {100 * gbs / 8000.0:5.1f}% of 8 TB/s{extra}", flush=True)
         del fn
         torch.cuda.empty_cache()
