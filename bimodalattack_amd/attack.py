@@ -46,6 +46,7 @@ from .dist import CandidateSharder
 from .fused import DeferredNormMissed, FusedInference
 from . import gemm_tuning
 from .hf_adapter import HFAdapter
+from .pgd import ImageUpdate
 from .layout import expected_row_counts, ragged_plan, ragged_rows, dynamic_width, segment_order, split_at_suffix, unique_rows
 from .utils import INIT_CHARS, FilterJob, get_nonascii_toks, is_oom, plan_chunk
 
@@ -250,8 +251,7 @@ class _RunState:
         self.image_original: Optional[Tensor] = None
         self.pending = None                    # a gradient pass computed / queued for the NEXT step: (gradients, seconds, span)
         self.fuse_pgd = False
-        self.apgd = None                       # pgd_rule "apgd": ops.ApgdState of this run (fresh per run, reference :1337)
-        self.l2 = None                         # pgd_norm "l2", plain rule: ops.L2Scratch of this run (workspace + norms)
+        self.update = None                     # pgd.ImageUpdate of this run, from its first PGD step on (rule, norm, their state)
         self.trace = None
         self.writer = None
         self.losses: List[float] = []
@@ -623,81 +623,27 @@ class BimodalAttack:
     def perform_pgd_step(self, image: Tensor, eps: float, alpha: float, image_grad: Tensor,
                          image_original: Tensor) -> Tensor:
         """x <- clamp(clamp(x - alpha*eps*sign(g), x0-eps, x0+eps), 0, 1) (:1030-1037)."""
-        x = image.detach()
-        if x.dtype != torch.float32:
-            raise TypeError("the PGD image must be float32 (the reference feeds ToTensor() output)")
-        out = ops.linf_step(x.contiguous(), image_grad.to(torch.float32).contiguous(),
-                            image_original.detach().contiguous(), eps, alpha)
-        return out.requires_grad_()
-
-    def perform_l2_step(self, image: Tensor, eps: float, alpha: float, image_grad: Tensor, image_original: Tensor,
-                        scratch: "ops.L2Scratch") -> Tensor:
-        """x <- P(x - alpha*eps * g/||g||), P onto the L2 ball of radius eps around x0 and into [0, 1] (pgd_norm "l2";
-        the reference has no such update): three launches of bma_l2_step, the norms stay on the device."""
-        x = image.detach()
-        if x.dtype != torch.float32:
-            raise TypeError("the PGD image must be float32 (the reference feeds ToTensor() output)")
-        out = ops.l2_step(x.contiguous(), image_grad.to(torch.float32).contiguous(),
-                          image_original.detach().contiguous(), eps, alpha, scratch=scratch)
-        return out.requires_grad_()
-
-    def perform_autopgd_step(self, image: Tensor, eps: float, image_grad: Tensor, image_original: Tensor,
-                             current_loss: Optional[float], iter_idx: int, state: "ops.ApgdState") -> Tensor:
-        """The reference's second update rule (:1039-1110): momentum step of eta = 2*eps, halved with a restart from the
-        best image when a checkpoint (every 10 steps) finds too few improvements.  `state` holds what the reference keeps
-        on `self` between calls; one launch of bma_apgd_step per call, its flags decided on the host."""
-        x = image.detach()
-        if x.dtype != torch.float32:
-            raise TypeError("the PGD image must be float32 (the reference feeds ToTensor() output)")
-        out = state.step(x.contiguous(), image_grad.to(torch.float32).contiguous(), image_original.detach().contiguous(),
-                         current_loss, iter_idx)
-        return out.requires_grad_()
+        return ImageUpdate("linf", "linf", eps, alpha).step(image, image_grad, image_original, None, 0)
 
     def _pgd_update(self, rs: "_RunState", sp: "_StepState") -> Tensor:
         """The step's image update by (EngineOptions.pgd_rule, pgd_norm).  The reference's `current_loss` (:421, :612) is
         the loss of the previous step, already on the host in every mode."""
         cfg = self.config
-        l2 = self.opt.pgd_norm == "l2"
-        if self.opt.pgd_rule != "apgd":
-            if not l2:
-                return self.perform_pgd_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original)
-            if rs.l2 is None:
-                rs.l2 = ops.L2Scratch(rs.image.device, rs.image.numel())
-                if sp.st is not None:
-                    sp.st["l2_x0"] = rs.image_original.detach().cpu().numpy()
-            if sp.st is not None:
-                x_in = rs.image.detach().cpu().numpy()
-            out = self.perform_l2_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original, rs.l2)
-            if sp.st is not None:
-                sp.st["l2"] = dict(x=x_in, g=sp.g_img.to(torch.float32).cpu().numpy(), out=out.detach().cpu().numpy(),
-                                   norms=rs.l2.norms.cpu().numpy())
-            return out
-        if rs.apgd is None:
-            rs.apgd = ops.ApgdState(cfg.eps, "l2" if l2 else "linf")
-        a = rs.apgd
-        cur = rs.losses[-1] if rs.losses else None
+        if rs.update is None:
+            rs.update = ImageUpdate(self.opt.pgd_rule, self.opt.pgd_norm, cfg.eps, cfg.alpha)
+        if (rs.update.rule, rs.update.norm) == ("linf", "linf"):      # the reference's rule, under the reference's name
+            return self.perform_pgd_step(rs.image, cfg.eps, cfg.alpha, sp.g_img, rs.image_original)
+        out = rs.update.step(rs.image, sp.g_img, rs.image_original, rs.losses[-1] if rs.losses else None, sp.i,
+                             record=sp.st is not None)
         if sp.st is not None:
-            if a.prev is None:
-                sp.st["apgd_x0"] = rs.image_original.detach().cpu().numpy()
-            x_in = rs.image.detach().cpu().numpy()
-            prev_in = x_in if a.prev is None else a.prev.cpu().numpy()
-            best_in = x_in if a.best is None else a.best.cpu().numpy()
-        out = self.perform_autopgd_step(rs.image, cfg.eps, sp.g_img, rs.image_original, cur, sp.i, a)
-        if sp.st is not None:
-            eta, take_best, restart = a.last
-            sp.st["apgd"] = dict(current_loss=cur, eta=eta, take_best=take_best, restart=restart, eta_next=a.eta,
-                                 count=a.count, best_loss=a.best_loss, last_best=a.last_best, x=x_in,
-                                 g=sp.g_img.to(torch.float32).cpu().numpy(), prev_in=prev_in, best_in=best_in,
-                                 prev_out=a.prev.cpu().numpy(), best_out=a.best.cpu().numpy())
-            if l2:
-                sp.st["apgd"].update(norm="l2", out=out.detach().cpu().numpy(), norms=a.scratch.norms.cpu().numpy())
+            sp.st.update(rs.update.stage_record())
         return out
 
     def _apgd_adopt(self, rs: "_RunState") -> None:
         """Several ranks: rank 0's image has just overwritten this rank's (dist.sync_state); the APGD state that the step
         derived from its own output follows it, so every rank's state stays rank 0's (no collective of its own)."""
-        if rs.apgd is not None and self.shard.enabled and self.shard.rank != 0:
-            rs.apgd.adopt(rs.image)
+        if rs.update is not None and self.shard.enabled and self.shard.rank != 0:
+            rs.update.adopt(rs.image)
 
     # ------------------------------------------------------------ sampling
     def _width(self, step: int) -> int:
@@ -1440,8 +1386,8 @@ class BimodalAttack:
                 rs.writer.close()
 
         self.final_image = rs.image
-        self.apgd_state = rs.apgd                # pgd_rule "apgd": the rule's state after the last step (None otherwise)
-        self.l2_scratch = rs.l2 if rs.apgd is None else rs.apgd.scratch   # pgd_norm "l2": the last step's norms (None otherwise)
+        self.apgd_state = rs.update.apgd if rs.update is not None else None      # pgd_rule "apgd": the rule's state after the last step
+        self.l2_scratch = rs.update.scratch if rs.update is not None else None   # pgd_norm "l2": the last step's norms
         k = rs.losses.index(min(rs.losses))
         return BimodalAttackResult(
             best_loss=rs.losses[k], best_string=rs.strings[k], losses=rs.losses, strings=rs.strings,

@@ -183,7 +183,7 @@ class EngineOptions:
     # The one option that changes results: opt-in, never a default.
     pgd_rule: str = "linf"
     # The threat model of that update: "linf" = the box |x - x0| <= eps of both reference rules; "l2" = the ball
-    # ||x - x0||_2 <= eps (eps in pixel units of the [0,1] image; csrc/l2_step.hip, contract in include/bma.h), which the
+    # ||x - x0||_2 <= eps (eps in pixel units of the [0,1] image; csrc/image_step.hip, contract in include/bma.h), which the
     # reference does not have.  Orthogonal to pgd_rule: ("linf", "l2") is plain L2 PGD with a step of alpha*eps along
     # g/||g||, ("apgd", "l2") is auto-PGD in the ball.  Changes results like pgd_rule: opt-in, never a default.
     pgd_norm: str = "linf"

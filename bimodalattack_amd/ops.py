@@ -57,17 +57,34 @@ def _stream(dev: torch.device) -> int:
 
 
 # ---------------------------------------------------------------------------
+def _images(name: str, *ts: torch.Tensor) -> torch.device:
+    """The image operands of an update rule: contiguous float32 tensors of one shape on one GPU."""
+    dev = _need_gpu(*ts)
+    for t in ts:
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != ts[0].shape:
+            raise ValueError(f"{name} wants {('three', 'five')[len(ts) > 3]} contiguous float32 tensors of one shape")
+    return dev
+
+
+def _out_like(x: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if out is None:
+        return torch.empty_like(x)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != x.device:
+        raise ValueError("bad out tensor")
+    return out
+
+
+def _own_state(name: str, x: torch.Tensor, out: torch.Tensor, prev: torch.Tensor, best: torch.Tensor) -> None:
+    ptrs = {t.data_ptr() for t in (x, out)}
+    if prev.data_ptr() == best.data_ptr() or ptrs & {prev.data_ptr(), best.data_ptr()}:
+        raise ValueError(f"{name}: prev and best are state buffers of their own (only out may alias x)")
+
+
 def linf_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, eps: float, alpha: float,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """clamp(clamp(x - (alpha*eps)*sign(g), x0-eps, x0+eps), 0, 1)  -- reference :1030-1037."""
-    dev = _need_gpu(x, g, x0)
-    for t in (x, g, x0):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != x.shape:
-            raise ValueError("linf_step wants three contiguous float32 tensors of one shape")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != dev:
-        raise ValueError("bad out tensor")
+    dev = _images("linf_step", x, g, x0)
+    out = _out_like(x, out)
     step = float(alpha * eps)  # the reference multiplies the two Python floats first (:1033)
     check("bma_linf_step", lib.bma_linf_step(x.data_ptr(), g.data_ptr(), x0.data_ptr(), x.numel(), float(eps), step,
                                              out.data_ptr(), _stream(dev)))
@@ -77,18 +94,10 @@ def linf_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, eps: float, al
 def apgd_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, prev: torch.Tensor, best: torch.Tensor, eps: float,
               eta: float, take_best: bool, restart: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The per-pixel part of one auto-PGD call (reference :1039-1110; include/bma.h): updates `prev` and `best` in place
-    and returns the new image (`out` may be `x`).  The decisions are the host's (ApgdState.decide)."""
-    dev = _need_gpu(x, g, x0, prev, best)
-    for t in (x, g, x0, prev, best):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != x.shape:
-            raise ValueError("apgd_step wants five contiguous float32 tensors of one shape")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != dev:
-        raise ValueError("bad out tensor")
-    ptrs = {t.data_ptr() for t in (x, out)}
-    if prev.data_ptr() == best.data_ptr() or ptrs & {prev.data_ptr(), best.data_ptr()}:
-        raise ValueError("apgd_step: prev and best are state buffers of their own (only out may alias x)")
+    and returns the new image (`out` may be `x`).  The decisions are the host's (pgd.ApgdState.decide)."""
+    dev = _images("apgd_step", x, g, x0, prev, best)
+    out = _out_like(x, out)
+    _own_state("apgd_step", x, out, prev, best)
     check("bma_apgd_step", lib.bma_apgd_step(x.data_ptr(), g.data_ptr(), x0.data_ptr(), prev.data_ptr(), best.data_ptr(),
                                              x.numel(), float(eps), float(eta), int(bool(take_best)), int(bool(restart)),
                                              out.data_ptr(), _stream(dev)))
@@ -118,14 +127,8 @@ def l2_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, eps: float, alph
             out: Optional[torch.Tensor] = None, scratch: Optional[L2Scratch] = None) -> torch.Tensor:
     """Plain PGD in the L2 ball of radius eps around x0 (include/bma.h, a5c): P(x - (alpha*eps) * g/(||g|| + 1e-10)),
     P = scale back onto the ball, then clamp to [0, 1].  `scratch.norms` holds the call's norms afterwards."""
-    dev = _need_gpu(x, g, x0)
-    for t in (x, g, x0):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != x.shape:
-            raise ValueError("l2_step wants three contiguous float32 tensors of one shape")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != dev:
-        raise ValueError("bad out tensor")
+    dev = _images("l2_step", x, g, x0)
+    out = _out_like(x, out)
     scratch = _l2_scratch(scratch, x)
     step = float(alpha * eps)  # the product of the two Python floats, as linf_step
     check("bma_l2_step", lib.bma_l2_step(x.data_ptr(), g.data_ptr(), x0.data_ptr(), x.numel(), float(eps), step,
@@ -138,17 +141,9 @@ def apgd_l2_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, prev: torch
                  scratch: Optional[L2Scratch] = None) -> torch.Tensor:
     """The per-pixel part of one auto-PGD call in the L2 ball (include/bma.h, a5c): flags, state and aliasing rules of
     `apgd_step`, the box replaced by the ball."""
-    dev = _need_gpu(x, g, x0, prev, best)
-    for t in (x, g, x0, prev, best):
-        if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != x.shape:
-            raise ValueError("apgd_l2_step wants five contiguous float32 tensors of one shape")
-    if out is None:
-        out = torch.empty_like(x)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != x.shape or out.device != dev:
-        raise ValueError("bad out tensor")
-    ptrs = {t.data_ptr() for t in (x, out)}
-    if prev.data_ptr() == best.data_ptr() or ptrs & {prev.data_ptr(), best.data_ptr()}:
-        raise ValueError("apgd_l2_step: prev and best are state buffers of their own (only out may alias x)")
+    dev = _images("apgd_l2_step", x, g, x0, prev, best)
+    out = _out_like(x, out)
+    _own_state("apgd_l2_step", x, out, prev, best)
     scratch = _l2_scratch(scratch, x)
     check("bma_apgd_l2_step", lib.bma_apgd_l2_step(x.data_ptr(), g.data_ptr(), x0.data_ptr(), prev.data_ptr(),
                                                    best.data_ptr(), x.numel(), float(eps), float(eta),
@@ -157,73 +152,11 @@ def apgd_l2_step(x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, prev: torch
     return out
 
 
-class ApgdState:
-    """What the reference's perform_autopgd_step keeps between calls (:1052-1061), for ONE run: eta, the best loss, the
-    loss at the last checkpoint and the improvement count as Python floats / ints (as the reference keeps them), and the
-    previous and best images as device buffers that only the kernel writes.  `decide` turns the call's (current_loss,
-    step index) into the kernel's flags without touching the device."""
-
-    MOMENTUM, RHO, INTERVAL = 0.75, 0.75, 10
-
-    def __init__(self, eps: float, norm: str = "linf"):
-        if norm not in ("linf", "l2"):
-            raise ValueError(f"ApgdState: norm must be 'linf' or 'l2', got {norm!r}")
-        self.eps = eps
-        self.norm = norm                      # "l2": the ball instead of the box (bma_apgd_l2_step); decide() is the same
-        self.scratch: Optional[L2Scratch] = None
-        self.started = False
-        self.eta = 2 * eps                    # initial step size (:1058); config.alpha is not used
-        self.best_loss = float("inf")
-        self.last_best = float("inf")
-        self.count = 0
-        self.prev: Optional[torch.Tensor] = None
-        self.best: Optional[torch.Tensor] = None
-        self.last = None                      # (eta, take_best, restart) of the latest call
-
-    def decide(self, current_loss: Optional[float], i: int) -> Tuple[float, bool, bool]:
-        """(eta of this call's descent step, take_best, restart); advances the host state as the reference's call does."""
-        if not self.started:
-            self.started = True
-            self.best_loss = current_loss if current_loss is not None else float("inf")
-            self.last_best = self.best_loss
-        eta, take_best, restart = self.eta, False, False
-        if current_loss is not None:
-            if current_loss < self.best_loss:
-                self.best_loss = current_loss
-                take_best = True
-            if current_loss < self.last_best:
-                self.count += 1
-            if (i + 1) % self.INTERVAL == 0:
-                if self.count / self.INTERVAL < self.RHO or self.best_loss == self.last_best:
-                    self.eta /= 2
-                    restart = True
-                self.count = 0
-                self.last_best = self.best_loss
-        self.last = (eta, take_best, restart)
-        return self.last
-
-    def step(self, x: torch.Tensor, g: torch.Tensor, x0: torch.Tensor, current_loss: Optional[float], i: int) -> torch.Tensor:
-        """One call of the rule: a fresh output tensor (never `prev` or `best` themselves)."""
-        if self.prev is None:
-            self.prev, self.best = x.clone(), x.clone()
-        eta, take_best, restart = self.decide(current_loss, i)
-        if self.norm == "l2":
-            if self.scratch is None:
-                self.scratch = L2Scratch(x.device, x.numel())
-            return apgd_l2_step(x, g, x0, self.prev, self.best, self.eps, eta, take_best, restart, scratch=self.scratch)
-        return apgd_step(x, g, x0, self.prev, self.best, self.eps, eta, take_best, restart)
-
-    def adopt(self, image: torch.Tensor) -> None:
-        """Several ranks: rank 0's copy of the image returned by the latest call has overwritten this rank's -- take the
-        state that call derived from its own output (best, and prev after a restart) from the synced pixels instead."""
-        if self.last is None:
-            return
-        _, take_best, restart = self.last
-        with torch.no_grad():
-            if take_best:
-                self.best.copy_(image.detach())
-            if restart:
-                self.prev.copy_(image.detach())
+def __getattr__(name: str):       # ApgdState lives in pgd.py, which imports this module; the old import path keeps working
+    if name == "ApgdState":
+        from .pgd import ApgdState
+        return ApgdState
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 # ---------------------------------------------------------------------------

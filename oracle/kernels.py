@@ -7,7 +7,8 @@ path.  Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s
 
 Parity status: PINNED.  Every function here is checked against golden vectors
 captured from the real reference (``tests/golden/make_golden.py`` ->
-``tests/golden/g1..g6``) by ``tests/test_oracle_golden.py``.
+``tests/golden/g1..g6``) by ``tests/test_oracle_golden.py``; the auto-PGD restatement against ``g8_apgd_unit``
+by ``tests/test_apgd.py``.  The L2 restatements have no reference: ``tests/test_pgd_l2.py`` holds them to the contract.
 
 Citations are into /root/reference/bimodalattack/bimodal_attack.py unless a
 file is named.
@@ -18,6 +19,7 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
+import torch
 
 
 # --------------------------------------------------------------------------
@@ -42,6 +44,117 @@ def linf_step(x: np.ndarray, g: np.ndarray, x0: np.ndarray, eps: float, alpha: f
     y = np.where(y < np.float32(0), np.float32(0), y)
     y = np.where(y > np.float32(1), np.float32(1), y)
     return y.astype(np.float32)
+
+
+# --------------------------------------------------------------------------
+# a5b -- auto-PGD L-inf step (reference :1039-1110), the per-pixel part of one call
+# --------------------------------------------------------------------------
+def _tmin(a, b):
+    """torch.min(a, b): NaN from either operand, the first operand on a tie."""
+    r = np.where(b < a, b, a)
+    return np.where(np.isnan(a), a, np.where(np.isnan(b), b, r))
+
+
+def _tmax(a, b):
+    r = np.where(a < b, b, a)
+    return np.where(np.isnan(a), a, np.where(np.isnan(b), b, r))
+
+
+def _clamp01(y):
+    y = np.where(y < 0, np.float32(0), y)
+    return np.where(y > 1, np.float32(1), y)
+
+
+def apgd_restated(x, g, x0, prev, best, eps, eta, take_best, restart):
+    """One call of the rule's per-pixel part, each operation rounded in float32 as the reference's torch ops round it.
+    Returns (out, prev, best) after the call."""
+    x, g, x0, prev, best = (np.asarray(a, np.float32) for a in (x, g, x0, prev, best))
+    if restart and not take_best:
+        return best.copy(), best.copy(), best.copy()
+    with np.errstate(invalid="ignore"):
+        s = (g > 0).astype(np.float32) - (g < 0).astype(np.float32)
+        hi, lo = x0 + np.float32(eps), x0 - np.float32(eps)
+        z = _clamp01(_tmax(_tmin(x - np.float32(eta) * s, hi), lo))
+        m = (x + np.float32(0.75) * (z - x)) + np.float32(0.25) * (x - prev)
+        new = _clamp01(_tmax(_tmin(m, hi), lo))
+    return new, (new if restart else x).copy(), (new if take_best else best).copy()
+
+
+def same_bits(a, b) -> bool:
+    """Equal bit for bit, any NaN equal to any NaN (torch's scalar and vector paths write different NaN payloads)."""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint32), b[~nb].view(np.uint32)))
+
+
+# --------------------------------------------------------------------------
+# a5c -- both rules in the L2 ball (no reference: the contract of include/bma.h, restated in torch fp32 ops)
+# --------------------------------------------------------------------------
+ULP = 2.0 ** -24          # one fp32 rounding, relative
+
+
+def as_f32(a):
+    return torch.as_tensor(np.asarray(a, np.float32))
+
+
+def f32_scalar(v):
+    """A Python float rounded to fp32 the way the C ABI's `float` parameter rounds it."""
+    return torch.tensor(float(v), dtype=torch.float32)
+
+
+def _nrm(v):
+    """nrm(v) = float32(sqrt(sum double(v_i)^2)): fp64 accumulation, rounded once."""
+    return v.double().pow(2).sum().sqrt().to(torch.float32)
+
+
+def l2_clamp01(y):
+    """compare+select: keeps -0.0, propagates NaN."""
+    y = torch.where(y < 0, torch.zeros((), dtype=torch.float32), y)
+    return torch.where(y > 1, torch.ones((), dtype=torch.float32), y)
+
+
+def _project(y, x0, eps):
+    """(clamp01(x0 + (y - x0) * f), nrm(y - x0)),  f = minimum(eps / nrm, 1): a zero norm gives inf and f = 1."""
+    d = y - x0
+    nd = _nrm(d)
+    f = torch.minimum(eps / nd, torch.ones((), dtype=torch.float32))
+    return l2_clamp01(x0 + d * f), nd
+
+
+def l2_descent(x, g, step):
+    ng = _nrm(g)
+    u = g / (ng + f32_scalar(1e-10))
+    return x - step * u, ng             # multiply, then subtract
+
+
+def l2_restated(x, g, x0, eps, step):
+    """One plain L2 step, fp32 operation by operation in the order of the contract.  Returns (out, norms[2]) as numpy."""
+    x, g, x0 = as_f32(x), as_f32(g), as_f32(x0)
+    y, ng = l2_descent(x, g, f32_scalar(step))
+    out, nd = _project(y, x0, f32_scalar(eps))
+    return out.numpy(), np.array([ng.item(), nd.item()], np.float32)
+
+
+def apgd_l2_restated(x, g, x0, prev, best, eps, eta, take_best, restart):
+    """One auto-PGD call in the L2 ball.  Returns (out, prev, best, norms[3]) after the call; norms is None on the
+    "restart without take_best" shortcut, which reads only `best` and leaves the norms alone."""
+    x, g, x0, prev, best = (as_f32(a) for a in (x, g, x0, prev, best))
+    if restart and not take_best:
+        b = best.numpy()
+        return b.copy(), b.copy(), b.copy(), None
+    y, ng = l2_descent(x, g, f32_scalar(eta))
+    z, nd = _project(y, x0, f32_scalar(eps))
+    m = (x + f32_scalar(0.75) * (z - x)) + f32_scalar(0.25) * (x - prev)
+    new, nm = _project(m, x0, f32_scalar(eps))
+    new = new.numpy()
+    return (new, (new if restart else x.numpy()).copy(), (new if take_best else best.numpy()).copy(),
+            np.array([ng.item(), nd.item(), nm.item()], np.float32))
+
+
+def dist64(a, b):
+    return float(np.sqrt(((np.asarray(a, np.float64) - np.asarray(b, np.float64)) ** 2).sum()))
 
 
 # --------------------------------------------------------------------------

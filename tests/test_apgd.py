@@ -1,5 +1,5 @@
-"""The auto-PGD image update (reference bimodal_attack.py:1039-1110, ``perform_autopgd_step``) on the CPU: a float32
-restatement of the rule equal bit for bit to the reference's own outputs (tests/golden/g8_apgd_unit.npz), the host-state
+"""The auto-PGD image update (reference bimodal_attack.py:1039-1110, ``perform_autopgd_step``) on the CPU: the float32
+restatement of the rule (oracle/kernels.py) equal bit for bit to the reference's own outputs (tests/golden/g8_apgd_unit.npz), the host-state
 class's eta / flag sequence, the C entry point's argument checks, and the ``pgd_rule`` engine option.  The kernel itself
 is held to the same restatement in test_apgd_gpu.py."""
 
@@ -9,47 +9,7 @@ import numpy as np
 import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-F = np.float32
-
-
-def _tmin(a, b):
-    """torch.min(a, b): NaN from either operand, the first operand on a tie."""
-    r = np.where(b < a, b, a)
-    return np.where(np.isnan(a), a, np.where(np.isnan(b), b, r))
-
-
-def _tmax(a, b):
-    r = np.where(a < b, b, a)
-    return np.where(np.isnan(a), a, np.where(np.isnan(b), b, r))
-
-
-def _clamp01(y):
-    y = np.where(y < 0, F(0), y)
-    return np.where(y > 1, F(1), y)
-
-
-def apgd_restated(x, g, x0, prev, best, eps, eta, take_best, restart):
-    """One call of the rule's per-pixel part, each operation rounded in float32 as the reference's torch ops round it.
-    Returns (out, prev, best) after the call."""
-    x, g, x0, prev, best = (np.asarray(a, F) for a in (x, g, x0, prev, best))
-    if restart and not take_best:
-        return best.copy(), best.copy(), best.copy()
-    with np.errstate(invalid="ignore"):
-        s = (g > 0).astype(F) - (g < 0).astype(F)
-        hi, lo = x0 + F(eps), x0 - F(eps)
-        z = _clamp01(_tmax(_tmin(x - F(eta) * s, hi), lo))
-        m = (x + F(0.75) * (z - x)) + F(0.25) * (x - prev)
-        new = _clamp01(_tmax(_tmin(m, hi), lo))
-    return new, (new if restart else x).copy(), (new if take_best else best).copy()
-
-
-def same_bits(a, b) -> bool:
-    """Equal bit for bit, any NaN equal to any NaN (torch's scalar and vector paths write different NaN payloads)."""
-    a, b = np.asarray(a, F), np.asarray(b, F)
-    if a.shape != b.shape:
-        return False
-    na, nb = np.isnan(a), np.isnan(b)
-    return bool(np.array_equal(na, nb) and np.array_equal(a[~na].view(np.uint32), b[~nb].view(np.uint32)))
+from oracle.kernels import apgd_restated, same_bits
 
 
 def unit_calls():
@@ -84,7 +44,7 @@ def test_restatement_equals_the_reference_bit_for_bit():
 
 
 def test_host_state_gives_the_reference_eta_and_flags():
-    from bimodalattack_amd.ops import ApgdState
+    from bimodalattack_amd.pgd import ApgdState
     z, calls = unit_calls()
     st = ApgdState(float(z["eps"]))
     for i, cur, _, _, rec in calls:
@@ -98,7 +58,7 @@ def test_host_state_gives_the_reference_eta_and_flags():
 def test_host_state_on_the_trajectory_goldens():
     """The reference's own losses of each g8 run fed to ApgdState reproduce its eta / restart sequence."""
     import json
-    from bimodalattack_amd.ops import ApgdState
+    from bimodalattack_amd.pgd import ApgdState
     meta = json.load(open(os.path.join(GOLDEN, "g8_meta.json")))["cases"]
     assert set(meta) == {"llava_pgd", "llava_pgd_gcg", "llava_joint", "gemma3_pgd", "gemma3_joint"}
     for name, m in meta.items():

@@ -1,5 +1,5 @@
 """The auto-PGD image update on the MI355X: bma_apgd_step against the reference's own calls (g8_apgd_unit) and the
-float32 restatement of test_apgd.py, and whole runs with ``pgd_rule="apgd"`` against the reference's trajectories
+float32 restatement of oracle/kernels.py, and whole runs with ``pgd_rule="apgd"`` against the reference's trajectories
 (g8_*), checked in two layers as test_attack_gpu.check_against_golden checks the default rule."""
 
 import json
@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_apgd import apgd_restated, same_bits, unit_calls
+from oracle.kernels import apgd_restated, same_bits
+from test_apgd import unit_calls
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -70,6 +71,36 @@ def test_kernel_equals_the_restatement_at_every_size(n, offset):
             for got, w, what in zip((out, p, b), want, ("out", "prev", "best")):
                 assert same_bits(got.cpu().numpy(), w), (n, offset, take_best, restart, what)
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_kernel_grid_stride_wrap_and_tail(offset):
+    """More float4 groups than the 2048 x 256 lanes of the largest grid, so lanes come round a second time, and a tail of 3
+    behind them; one float off the 16-byte grid the scalar kernel takes all of it and wraps four times."""
+    from bimodalattack_amd import ops
+    n = 2048 * 256 * 4 + 4 * 256 + 3
+    rs = np.random.RandomState(11)
+    eps = 64 / 255
+    x0 = rs.uniform(0, 1, n).astype(np.float32)
+    x = np.clip(x0 + rs.uniform(-eps, eps, n).astype(np.float32), 0, 1).astype(np.float32)
+    prev = np.clip(x0 + rs.uniform(-eps, eps, n).astype(np.float32), 0, 1).astype(np.float32)
+    best = rs.uniform(0, 1, n).astype(np.float32)
+    g = rs.standard_normal(n).astype(np.float32)
+    g[::1001] = np.nan
+
+    def dev(a):
+        buf = torch.empty(n + offset, dtype=torch.float32, device=DEV)
+        buf[offset:].copy_(torch.from_numpy(a))
+        return buf[offset:]
+
+    xd, gd, x0d = dev(x), dev(g), dev(x0)
+    for take_best in (False, True):
+        for restart in (False, True):
+            p, b = dev(prev), dev(best)
+            out = ops.apgd_step(xd, gd, x0d, p, b, eps, 2 * eps, take_best, restart)
+            want = apgd_restated(x, g, x0, prev, best, eps, 2 * eps, take_best, restart)
+            for got, w, what in zip((out, p, b), want, ("out", "prev", "best")):
+                assert same_bits(got.cpu().numpy(), w), (offset, take_best, restart, what)
 
 
 def test_kernel_refuses_aliased_state():

@@ -75,6 +75,28 @@ def test_linf_sizes_vs_oracle(ops, n):
     assert np.array_equal(bits(again), bits(got))
 
 
+@pytest.mark.parametrize("offset", [0, 1])
+def test_linf_grid_stride_wrap_and_tail(ops, offset):
+    """More float4 groups than the 2048 x 256 lanes of the largest grid, so lanes come round a second time, and a tail of 3
+    behind them; one float off the 16-byte grid the scalar kernel takes all of it and wraps four times."""
+    n = 2048 * 256 * 4 + 4 * 256 + 3
+    rs = np.random.RandomState(7)
+    x0 = rs.uniform(0, 1, n).astype(np.float32)
+    x = np.clip(x0 + rs.uniform(-0.3, 0.3, n), 0, 1).astype(np.float32)
+    g = rs.standard_normal(n).astype(np.float32)
+    g[::5] = 0
+    g[1::17] = np.nan
+    eps, alpha = 64 / 255, 4 / 255
+
+    def off(a):
+        buf = torch.empty(n + offset, dtype=torch.float32, device=DEV)
+        buf[offset:].copy_(torch.from_numpy(a))
+        return buf[offset:]
+
+    got = ops.linf_step(off(x), off(g), off(x0), eps, alpha).cpu().numpy()
+    assert np.array_equal(bits(got), bits(K.linf_step(x, g, x0, eps, alpha)))
+
+
 def test_linf_unaligned_and_empty(ops):
     rs = np.random.RandomState(0)
     n = 1001

@@ -1,5 +1,5 @@
 """The L2-ball PGD image update on the MI355X: bma_l2_step / bma_apgd_l2_step against the torch restatement of
-test_pgd_l2.py bit for bit (image, state and norms), their determinism and graph capture, and whole runs with
+oracle/kernels.py bit for bit (image, state and norms), their determinism and graph capture, and whole runs with
 ``pgd_norm="l2"`` under both rules: every traced step replayed through the restatement, the routes of the step loop, host
 reads, two ranks, and a full-size LLaVA-1.5-7B-shaped run.  The reference has no L2 update, so there is no golden."""
 
@@ -10,9 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from test_apgd import same_bits
+from oracle.kernels import ULP, apgd_l2_restated, dist64, l2_restated, same_bits
 from test_apgd_gpu import META5, META8, _HostReads, run_g8
-from test_pgd_l2 import ULP, apgd_l2_restated, dist64, l2_restated
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -102,6 +101,29 @@ def test_apgd_l2_kernel_equals_the_restatement_at_every_size(n, offset):
                     if what == "nan":
                         assert np.isnan(want[0]).all() and np.isnan(norms).all()
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_l2_grid_stride_wrap_and_tail(offset):
+    """More float4 groups than the 256 x 1024 lanes of the chain's grid and a tail of 3 behind them in the same launch; one
+    float off the 16-byte grid the scalar loop takes all of it and wraps four times.  Both rules, and the copy-only call."""
+    from bimodalattack_amd import ops
+    n = 256 * 1024 * 4 + 4 * 1024 + 3
+    x, g, x0, prev, best = _inputs(n)
+    sc = ops.L2Scratch(torch.device(DEV), n)
+    eps = _radii(n)[0]
+    xd, gd, x0d = _dev(x, offset), _dev(g, offset), _dev(x0, offset)
+    out = ops.l2_step(xd, gd, x0d, eps, 0.5, scratch=sc)
+    want, wn = l2_restated(x, g, x0, eps, 0.5 * eps)
+    assert same_bits(out.cpu().numpy(), want) and same_bits(sc.norms.cpu().numpy()[:2], wn)
+    for take_best, restart in ((True, True), (False, True)):
+        p, b = _dev(prev, offset), _dev(best, offset)
+        out = ops.apgd_l2_step(xd, gd, x0d, p, b, eps, 2 * eps, take_best, restart, scratch=sc)
+        want = apgd_l2_restated(x, g, x0, prev, best, eps, 2 * eps, take_best, restart)
+        for got, w, name in zip((out, p, b), want, ("out", "prev", "best")):
+            assert same_bits(got.cpu().numpy(), w), (offset, take_best, restart, name)
+        if want[3] is not None:
+            assert same_bits(sc.norms.cpu().numpy(), want[3]), (offset, take_best, restart)
 
 
 def test_l2_kernels_are_deterministic():
@@ -195,7 +217,7 @@ def run_l2(name, rule, over=None, trace=True, meta=None, **engine):
 def check_l2_trace(trace, res, eps, alpha, rule):
     """Every step's kernel output, state and norms equal the restatement applied to the engine's OWN recorded inputs; the
     host's flags equal ApgdState's logic applied to the engine's OWN losses.  Returns the steps that restarted."""
-    from bimodalattack_amd.ops import ApgdState
+    from bimodalattack_amd.pgd import ApgdState
     restarts = []
     if rule == "linf":
         x0 = trace[0]["l2_x0"]
