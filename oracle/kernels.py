@@ -325,3 +325,234 @@ def filter_ids(ids: np.ndarray, tokenizer) -> np.ndarray:
             "Consider setting filter_ids=False or trying a different optim_str_init"
         )
     return np.stack(keep)
+
+
+# --------------------------------------------------------------------------
+# backward elementwise kernels (csrc/fused_elementwise.hip: rmsnorm_bwd_kernel, swiglu_bwd_kernel, rope with sin_sign = -1)
+# --------------------------------------------------------------------------
+# No reference program: the formulas in the comment block above rmsnorm_bwd_kernel, evaluated in float64 on operands
+# already rounded to the model dtype, and the error bounds a correct fp32 evaluation of them keeps.  Written in torch
+# float64 (not numpy) so that the largest case can stay on the device; numpy arrays are accepted.  Used by
+# tests/test_backward_refs.py (CPU: the references against autograd, the bounds against a restatement of the kernels
+# and against mutants of it) and tests/test_backward_gpu.py (the kernels).
+from collections import namedtuple
+
+# dtype -> (significand bits p, exponent of the smallest normal number)
+_FORMATS = {torch.bfloat16: (8, -126), torch.float16: (11, -14), torch.float32: (24, -126)}
+U32 = 2.0 ** -24                         # one fp32 rounding, relative
+GELU_BETA, GELU_KAPPA = 0.7978845608028654, 0.044715   # sqrt(2/pi) and aten's kappa; the kernel rounds both to fp32
+SILU_DZERO, GELU_DZERO = -1.2785, -0.7525            # zeros of silu' and of gelu-tanh'
+
+
+def unit_roundoff(dt) -> float:
+    """u: half the spacing of dtype `dt` relative to a value (2^-8 bf16, 2^-11 fp16, 2^-24 fp32)."""
+    return 2.0 ** -_FORMATS[dt][0]
+
+
+def half_subnormal(dt) -> float:
+    """Half the subnormal spacing of `dt` (fp16: 2^-25): the absolute rounding error below the smallest normal."""
+    p, emin = _FORMATS[dt]
+    return 2.0 ** (emin - p)
+
+
+def f64(a):
+    return (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(torch.float64)
+
+
+def round_dt(a, dt):
+    """float64 -> the nearest value of `dt` (ties to even, gradual underflow, overflow to inf), as float64.  One
+    rounding, done on the float64 bits: a conversion through fp32 would round twice."""
+    a = f64(a)
+    p, emin = _FORMATS[dt]
+    e = ((a.view(torch.int64) >> 52) & 0x7FF) - 1023                  # floor(log2 |a|) of a normal double
+    k = torch.clamp(e, min=emin) - (p - 1)                            # exponent of the spacing of dt at a
+    q = ((k + 1023) << 52).view(torch.float64)
+    r = torch.round(a / q) * q                                        # torch.round: halves to even
+    top = (2.0 - 2.0 ** (1 - p)) * 2.0 ** (127 if dt != torch.float16 else 15)
+    r = torch.where(r.abs() > top, torch.sign(a) * float("inf"), r)
+    return torch.where(torch.isfinite(a), r, a)
+
+
+NormBwdRef = namedtuple("NormBwdRef", "ref dxn rg xk")
+
+
+def rmsnorm_bwd_ref(x, w, dy, eps, gemma, dsum=None) -> NormBwdRef:
+    """dxn = r*g - x*k per row, g = dy*w (Llama) or dy*(1+w) (Gemma), r = 1/sqrt(mean(x^2)+eps), k = r^3*sum(g*x)/D, in
+    float64 on operands (rows, D) already rounded to the model dtype; `eps` as the fp32 number the C entry point gets.
+    ref = dxn, or dsum + dxn given the gradient of the residual stream.  rg = |r*g| and xk = |x|*r^3*sum|g*x|/D are
+    the sizes of the two terms before they cancel, which is what an fp32 evaluation's error scales with."""
+    x, w, dy = f64(x), f64(w), f64(dy)
+    D = x.shape[-1]
+    eps = float(np.float32(eps))
+    g = dy * (1.0 + w if gemma else w)
+    r = 1.0 / torch.sqrt((x * x).mean(-1, keepdim=True) + eps)
+    k = r ** 3 * (g * x).sum(-1, keepdim=True) / D
+    dxn = r * g - x * k
+    rg = (r * g).abs()
+    xk = x.abs() * r ** 3 * (g * x).abs().sum(-1, keepdim=True) / D
+    return NormBwdRef(dxn if dsum is None else f64(dsum) + dxn, dxn, rg, xk)
+
+
+# The longest chain of fp32 roundings behind one output of rmsnorm_bwd_kernel: 32 sequential adds in a lane (4 chunks of
+# 8), 6 levels of the wave reduction and 4 partials = 42 adds, the product under the sum and dy*(1+w) = 45; the division,
+# square root and reciprocal of r = 3; r^3*tsg/D = 4; the two output products and the subtraction = 3.  55, rounded up
+# to a power of two, each taken as one relative rounding of a quantity no larger than M = rg + xk.  The count is of the
+# chain, not a worst case compounded through r^3: the roundings of a 42-term sum are independent and stay far below
+# 42 half-units together (tests/test_backward_refs.py records how much of the bound a faithful evaluation uses).
+NORM_BWD_C = 64
+
+
+def norm_bwd_tol(ref: NormBwdRef, dt, with_dsum: bool):
+    """Largest |got - ref.ref| a correct kernel leaves, per element: the one rounding to `dt` of the result, the fp32
+    evaluation (NORM_BWD_C roundings of the uncancelled size), the rounding's subnormal floor -- and with `dsum` the
+    rounding of dxn before the add, with its own floor."""
+    u, fl = unit_roundoff(dt), half_subnormal(dt)
+    tol = u * ref.ref.abs() + NORM_BWD_C * U32 * (ref.rg + ref.xk) + fl
+    if with_dsum:
+        tol = tol + u * ref.dxn.abs() + fl
+    return tol
+
+
+def gated_act_bwd_ref(gate, up, dy, act):
+    """(act64(gate), act'64(gate), d_gate = dy*up*act'(gate)) in float64; act 0 = SiLU, 1 = GELU-tanh with the kernel's
+    constants sqrt(2/pi) and 0.044715 (their rounding to fp32 is part of the kernel's error, counted below)."""
+    g, up, dy = f64(gate), f64(up), f64(dy)
+    if act == 0:
+        s = torch.sigmoid(g)
+        a, d = g * s, s * (1.0 + g * (1.0 - s))
+    else:
+        g2 = g * g
+        t = torch.tanh(GELU_BETA * (g + GELU_KAPPA * g2 * g))
+        a = 0.5 * g * (1.0 + t)
+        d = 0.5 * (1.0 + t) + 0.5 * g * (1.0 - t * t) * GELU_BETA * (1.0 + 3.0 * GELU_KAPPA * g2)
+    return a, d, dy * up * d
+
+
+# swiglu_bwd_kernel's act'(g) in fp32, first-order worst case in units of 2^-24 * (1 + |g|*(1 + 3*kappa*g^2 [GELU])).
+# Assumed accuracy of the device functions: expf within 3 ulp, tanhf within 5 ulp -- the OpenCL full-profile limits the
+# ROCm device library is written to; the HIP math-API table (which lists smaller figures) is not part of a ROCm install.
+#   SiLU, a = 3:  e = expf(-g): a.  1+e: a+1.  s = 1/(1+e): a+2 (relative, so at most a+2 absolute).  1-s: a+2.
+#     g*(1-s): (a+3)|g|.  1+..: (a+3)|g| + (1+|g|).  s*(..): + (a+2)(1+|g|) + (1+|g|)  ->  (2a+7)(1+|g|) = 13.
+#   GELU, b = 5:  inner = beta*fma(kappa, x^2*x, x): 5 relative.  t: b + 5*max|z|(1-tanh^2 z) = b + 2.25.
+#     0.5*(1+t): (b+4.25)/2.  1-t*t: 2b+6.5.  beta*(1+3*kappa*x^2): 6 relative.  The product of the three factors and
+#     the final add: (0.4*(2b+14.5) + 0.4)|x|(1+3 kappa x^2) + (b+4.25)/2 + 1  ->  at most 0.8b + 6.2 = 10.2.
+#   dy*up and the product with act': 2 more.  max(13, 10.2) + 2 = 15, rounded up to a power of two.
+D_GATE_C = 16
+
+
+def d_gate_tol(gate, up, dy, act, ref, dt):
+    """Largest |got - d_gate| a correct kernel leaves: one rounding to `dt`, D_GATE_C fp32 roundings of
+    M = |dy*up|*(1 + |g|*(1 + 3*kappa*g^2 [GELU])), the size act' is assembled from, and the subnormal floor."""
+    g, up, dy = f64(gate), f64(up), f64(dy)
+    m = (dy * up).abs() * (1.0 + g.abs() * (1.0 + (3.0 * GELU_KAPPA * g * g if act == 1 else 0.0)))
+    return unit_roundoff(dt) * ref.abs() + D_GATE_C * U32 * m + half_subnormal(dt)
+
+
+def d_up_interval(gate, dy, act, a64, dt):
+    """(lo, hi, ambiguous): d_up = dy * dt(act(gate)) with the activation rounded to `dt` first, as the forward kept
+    it.  The kernel's fp32 activation is within e = 8*2^-24*(|act| + 0.5|g| [GELU]) of act64 -- GELU's 0.5*x*(1+t)
+    loses 1+t to cancellation in the negative tail, where fp32 1+t is exactly 0 -- so its rounding is one of
+    a_lo = dt(act64-e) .. a_hi = dt(act64+e); the result lies between dy*a_lo and dy*a_hi, each end widened by its own
+    rounding to `dt` and the subnormal floor.  `ambiguous` marks the elements where a_lo != a_hi."""
+    g, dy = f64(gate), f64(dy)
+    u, fl = unit_roundoff(dt), half_subnormal(dt)
+    e = 8.0 * U32 * (a64.abs() + (0.5 * g.abs() if act == 1 else 0.0))
+    a_lo, a_hi = round_dt(a64 - e, dt), round_dt(a64 + e, dt)
+    p, q = dy * a_lo, dy * a_hi
+    lo, hi = torch.minimum(p, q), torch.maximum(p, q)
+    return lo - (u * lo.abs() + fl), hi + (u * hi.abs() + fl), a_lo != a_hi
+
+
+def rope_ref(q, cos, sin, sign, dt):
+    """dt(dt(q*cos) + dt(rotate_half(q)*sign*sin)), rotate_half(q) = cat(-q2, q1); q (B,H,L,Dh), cos/sin (1|B,L,Dh), all
+    values of `dt`; sign = -1 is the inverse rotation (the backward).  The kernel's rounding points: each product is
+    exact in float64 and rounded once, the sum is an fp32 add rounded to `dt` -- so the comparison is bit for bit."""
+    q, cos, sin = f64(q), f64(cos)[:, None], f64(sin)[:, None]
+    h = q.shape[-1] // 2
+    rot = torch.cat([-q[..., h:], q[..., :h]], -1)
+    a = round_dt(q * cos, dt).to(torch.float32)
+    b = round_dt(rot * float(sign) * sin, dt).to(torch.float32)
+    return round_dt((a + b).double(), dt)
+
+
+def _randn(shape, gen):
+    return torch.randn(shape, generator=gen, dtype=torch.float32)
+
+
+def norm_bwd_inputs(rows, D, dt, gemma, seed=0):
+    """(x, w, dy, dsum) on the CPU in `dt`.  Row 0 is plain (x = 2*randn); of six rows the other five are: all zeros,
+    x*1e-4 (eps dominates), x*100 (fp16 results near its subnormal range), one-hot (the two terms cancel to about
+    D*eps/x0^2 of their size), and dy = 0.  w = 0.3*randn (+1 for Llama), so Gemma weights come near zero."""
+    gen = torch.Generator().manual_seed(1000 * seed + D)
+    x, dy, dsum = 2.0 * _randn((rows, D), gen), _randn((rows, D), gen), _randn((rows, D), gen)
+    w = 0.3 * _randn((D,), gen) + (0.0 if gemma else 1.0)
+    if rows >= 6:
+        x[1] = 0.0
+        x[2] *= 1e-4
+        x[3] *= 100.0
+        x[4, 1:] = 0.0
+        x[4, 0] = 2.0
+        dy[5] = 0.0
+    return x.to(dt), w.to(dt), dy.to(dt), dsum.to(dt)
+
+
+def gated_bwd_inputs(n, dt, seed=0):
+    """(gate, up, dy) on the CPU in `dt`, n elements.  gate: an eighth on linspace(-30, 30), an eighth within 1e-2 of
+    the zero of silu', an eighth within 1e-2 of the zero of gelu-tanh' (where the derivative's terms cancel), then
+    0.0, -0.0, 88, -88 (saturated gates), the rest 4*randn; shuffled.  up = 2*randn, dy = randn."""
+    gen = torch.Generator().manual_seed(2000 * seed + n % 9973)
+    k = n // 8
+    near = lambda z: z + 1e-2 * (2.0 * torch.rand(k, generator=gen, dtype=torch.float32) - 1.0)
+    parts = [torch.linspace(-30.0, 30.0, k), near(SILU_DZERO), near(GELU_DZERO), torch.tensor([0.0, -0.0, 88.0, -88.0])]
+    parts.append(4.0 * _randn((n - sum(p.numel() for p in parts),), gen))
+    gate = torch.cat(parts)[torch.randperm(n, generator=gen)]
+    return gate.to(dt), (2.0 * _randn((n,), gen)).to(dt), _randn((n,), gen).to(dt)
+
+
+# the cases both test files run
+NORM_BWD_D = {torch.bfloat16: [8, 256, 2048, 2056, 2560, 4096, 5120, 6152, 8192],     # 16-byte chunks per lane 1..4, full
+              torch.float16: [8, 256, 2048, 2056, 2560, 4096, 5120, 6152, 8192],      # and partly filled last rounds
+              torch.float32: [4, 128, 1024, 1028, 2560, 4096]}
+NORM_BWD_EPS = {False: 1e-5, True: 1e-6}            # Llama's and Gemma's rms_norm_eps
+GATED_BWD_N = [8, 24, 65536]                        # one chunk, three chunks, many workgroups
+GATED_BWD_WRAP_N = (1048576 + 256 + 3) * 8          # bf16: past the 4096 x 256 chunks one pass of the backward's grid covers
+
+
+def rope_inputs(B, H, L, Dh, cb, dt, seed=0):
+    """(q, cos, sin, dq) on the CPU in `dt`: q and dq as strided (B,H,L,Dh) views of fused (B,L,3*H*Dh) projections,
+    cos/sin (cb,L,Dh)."""
+    gen = torch.Generator().manual_seed(seed + Dh + L)
+    view = lambda t: t[..., H * Dh:2 * H * Dh].view(B, L, H, Dh).transpose(1, 2)
+    q = view(_randn((B, L, 3 * H * Dh), gen).to(dt))
+    dq = view(_randn((B, L, 3 * H * Dh), gen).to(dt))
+    ang = torch.rand((cb, L, Dh // 2), generator=gen) * 6.28
+    emb = torch.cat([ang, ang], -1)
+    return q, emb.cos().to(dt), emb.sin().to(dt), dq
+
+
+def rope_round_trip_tol(q, dt):
+    """Largest |inverse(forward(x)) - x| per element, in roundings u of n = sqrt(x_i^2 + partner_i^2), the size of the
+    pair the rotation mixes (it is orthogonal, so nothing grows): each pass rounds two products and their sum,
+    u*(|x c| + |p s|) + u*|y| <= 2un; the forward's errors reach one output through c and s, (|c| + |s|)*2un <= 2*sqrt(2)*un;
+    cos and sin are themselves rounded to the dtype, so c^2 + s^2 is 1 only to 2u.  2 + 2*sqrt(2) + 2 = 6.83, with the
+    second-order terms 7.  (Two roundings are not enough: rope_ref itself reaches 3.97 on rope_inputs.)"""
+    qd = f64(q)
+    h = qd.shape[-1] // 2
+    p = torch.cat([qd[..., h:], qd[..., :h]], -1)
+    return 7.0 * unit_roundoff(dt) * torch.sqrt(qd * qd + p * p) + half_subnormal(dt)
+
+
+def norm_bwd_ratio(got, x, w, dy, eps, gemma, dsum, dt) -> float:
+    """Worst |got - ref| / bound over the elements: the check is `<= 1`."""
+    ref = rmsnorm_bwd_ref(x, w, dy, eps, gemma, dsum)
+    return ((f64(got) - ref.ref).abs() / norm_bwd_tol(ref, dt, dsum is not None)).max().item()
+
+
+def gated_bwd_ratios(dg, du, gate, up, dy, act, dt):
+    """(worst |d_gate error| / bound, worst distance of d_up from its interval's centre / half-width -- both checks are
+    `<= 1` -- and the share of elements whose activation may round either way)."""
+    a64, _, ref = gated_act_bwd_ref(gate, up, dy, act)
+    rg = ((f64(dg) - ref).abs() / d_gate_tol(gate, up, dy, act, ref, dt)).max().item()
+    lo, hi, amb = d_up_interval(gate, dy, act, a64, dt)
+    ru = ((f64(du) - 0.5 * (lo + hi)).abs() / (0.5 * (hi - lo))).max().item()
+    return rg, ru, amb.double().mean().item()

@@ -750,7 +750,8 @@ def test_splice_rows_is_splice_then_gather(dtype, scale):
 # ------------------------------------------------------------------ fused ops under autograd
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_fused_backward_matches_eager_autograd(dtype):
-    """dL/dx of the fused Functions against autograd through the eager HuggingFace modules."""
+    """dL/dx of the fused Functions against autograd through the eager HuggingFace modules.
+    (The numerical bound, element by element against float64, is in tests/test_backward_gpu.py.)"""
     from bimodalattack_amd import ops
     from transformers.models.gemma3.modeling_gemma3 import Gemma3RMSNorm
     from transformers.models.llama.modeling_llama import LlamaRMSNorm, apply_rotary_pos_emb
