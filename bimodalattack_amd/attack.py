@@ -41,7 +41,7 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .config import BimodalAttackConfig, BimodalAttackResult, EngineOptions
+from .config import BimodalAttackConfig, BimodalAttackResult, EngineOptions, mellowmax_alpha
 from .dist import CandidateSharder
 from .fused import DeferredNormMissed, FusedInference
 from . import gemm_tuning
@@ -294,6 +294,10 @@ class BimodalAttack:
         self.model, self.tokenizer, self.processor = model, tokenizer, processor
         self.config, self.normalize = config, normalize
         self.opt = options or EngineOptions.from_env()
+        # loss_rule "mellowmax": the one rule that reads config.mellowmax_alpha (checked here, when the rule is selected)
+        self._mm_alpha = mellowmax_alpha(config) if self.opt.loss_rule == "mellowmax" else None
+        if self._mm_alpha is not None:
+            logger.info(f"Target loss: mellowmax, alpha = {self._mm_alpha} (loss_rule; the default is the cross-entropy)")
         if model.device.type != "cuda":
             raise RuntimeError(
                 f"bimodalattack_amd runs on an AMD GPU only (model is on {model.device}); there is no CPU path. "
@@ -565,6 +569,20 @@ class BimodalAttack:
             self._gp_flag = bool(ok and hf.shared_prefix_configs())
         return self._gp_flag
 
+    def _target_loss(self, logits: Tensor, scoring: bool = False):
+        """The target loss by EngineOptions.loss_rule.  Gradient pass: the (T, V) target rows of the one sequence -> the scalar
+        loss, differentiable (the kernel's own dlogits).  scoring=True: (B, T, V) -> (loss (B,) fp32, early-stop hit or
+        None); the hit is the argmax test of the cross-entropy kernel's row pass under either rule."""
+        mm, want_hit = self._mm_alpha is not None, bool(scoring and self.config.early_stop)
+        if not scoring:
+            return (ops.TargetMellowmax.apply(logits, self.labels, self._mm_alpha) if mm
+                    else ops.TargetCrossEntropy.apply(logits, self.labels))
+        if mm:
+            hit = ops.ce_target(logits, self.labels, want_match=True)[1] if want_hit else None
+            return ops.mellowmax_target(logits, self.labels, self._mm_alpha)[0], hit
+        loss, hit, _, _ = ops.ce_target(logits, self.labels, want_match=want_hit)
+        return loss, hit
+
     def _gradient_eager(self, optim_ids: Tensor, image: Optional[Tensor] = None):
         """One forward/backward at batch 1.  The one-hot is never built: its gradient is
         (dL/d suffix embeddings) @ E^T, the same product autograd would form."""
@@ -585,7 +603,7 @@ class BimodalAttack:
                 logits = self.hf.target_logits(x[:, :-1], self.T, rows_only=True)
             else:
                 logits = self.hf.target_logits(x, self.T, rows_only=False)
-        loss = ops.TargetCrossEntropy.apply(logits[0], self.labels)
+        loss = self._target_loss(logits[0])
         wanted = ([emb] if cfg.gcg_attack else []) + ([image] if cfg.pgd_attack else [])
         grads = list(torch.autograd.grad(loss, wanted))
         g_tok = None
@@ -924,7 +942,7 @@ class BimodalAttack:
             # the row list straight from the segments and the table: the padded (blocks, L, D) block is never built
             rows = ops.splice(segs, blocks, E, maps.ids, hf.emb_scale, rows=maps.flat).unsqueeze(0)
             logits = hf.target_logits_ragged(rows, self.T, cache, maps)
-            loss, hit, _, _ = ops.ce_target(logits, self.labels, want_match=cfg.early_stop)
+            loss, hit = self._target_loss(logits, scoring=True)
             return loss, hit
 
         if real is not None:
@@ -1120,7 +1138,7 @@ class BimodalAttack:
                 if scored is not None:
                     loss, hit = scored
                 else:
-                    loss, hit, _, _ = ops.ce_target(logits, self.labels, want_match=cfg.early_stop)
+                    loss, hit = self._target_loss(logits, scoring=True)
                 if self.score_log is not None and logits is not None:
                     self.score_log.append(dict(chunk_at=s, b=b, logits_bad=(~torch.isfinite(logits.float())).sum(),
                                                    x_bad=None if x is None else (~torch.isfinite(x.float())).sum()))
@@ -1795,7 +1813,7 @@ class _GradPrefix:
         tail = torch.cat([emb, a.seg["after"], a.seg["target_in"]], dim=1)
         with torch.enable_grad(), a.fused:
             logits = a.hf.target_logits_behind_grad_prefix(tail, a.T, self.rec)
-            loss = ops.TargetCrossEntropy.apply(logits[0], a.labels)
+            loss = a._target_loss(logits[0])
         g_emb, g_img = torch.autograd.grad(loss, [emb, self.image])
         with torch.no_grad():
             g_tok = (g_emb[0] @ E.t()).unsqueeze(0)
@@ -1840,7 +1858,7 @@ class _GradPrefix:
         tail = torch.cat([emb, a.seg["after"], a.seg["target_in"]], dim=1)
         with torch.enable_grad(), a.fused:
             logits = a.hf.target_logits_behind_grad_prefix(tail, a.T, self._cache)
-            loss = ops.TargetCrossEntropy.apply(logits[0], a.labels)
+            loss = a._target_loss(logits[0])
         (g_emb,) = torch.autograd.grad(loss, [emb])
         with torch.no_grad():
             g_tok = (g_emb[0] @ E.t()).unsqueeze(0)

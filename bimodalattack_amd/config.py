@@ -28,8 +28,8 @@ class BimodalAttackConfig:
     topk: int = 256
     n_replace: int = 1
     buffer_size: int = 0
-    use_mellowmax: bool = False          # declared by the reference, never read
-    mellowmax_alpha: float = 1.0         # declared by the reference, never read
+    use_mellowmax: bool = False          # declared by the reference, never read (EngineOptions.loss_rule selects the loss)
+    mellowmax_alpha: float = 1.0         # read under EngineOptions.loss_rule="mellowmax" only (the reference never reads it)
     early_stop: bool = False
     allow_non_ascii: bool = False
     filter_ids: bool = True
@@ -75,7 +75,7 @@ class EngineOptions:
     """Knobs of the MI355X engine that the reference has no field for: the ones a test or bench.py flips.
 
     Read from keyword arguments of :func:`bimodalattack_amd.run` or from the environment (``BMA_<NAME>``), never from
-    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule`` and ``pgd_norm`` only changes speed (tests/test_attack_gpu.py runs the reference's golden
+    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule``, ``pgd_norm`` and ``loss_rule`` only changes speed (tests/test_attack_gpu.py runs the reference's golden
     trajectories with each restructuring off).  Finer switches that exist for A/B measurements only are module constants
     read from the environment once (round 5: 42 options -> 27): ``ops.OWN_KERNELS`` (each hand-written batch-1 kernel),
     ``attack.MASKLESS_B1_ATTENTION`` / ``CHUNK_QUANTUM`` / ``EMULATE_WORLD``, ``fused.FUSE_QK_ROPE``,
@@ -187,6 +187,28 @@ class EngineOptions:
     # reference does not have.  Orthogonal to pgd_rule: ("linf", "l2") is plain L2 PGD with a step of alpha*eps along
     # g/||g||, ("apgd", "l2") is auto-PGD in the ball.  Changes results like pgd_rule: opt-in, never a default.
     pgd_norm: str = "linf"
+    # The target loss of every scoring forward and gradient pass: "ce" = the reference's mean cross-entropy over the target
+    # rows; "mellowmax" = nanoGCG's objective, the reference's own `mellowmax` (utils.py:35-36, shipped and never called)
+    # over the negated raw target logits with alpha = config.mellowmax_alpha (csrc/mellowmax_target.hip, contract in
+    # include/bma.h; losses may be negative).  Changes results like pgd_rule: opt-in, never a default.
+    # `config.use_mellowmax` does NOT select it: the dataclass behaves as the reference's, which ignores that field.
+    # (Set like every option -- keyword of run() / from_env, or BMA_LOSS_RULE -- but a plain attribute, not a dataclass
+    # field: the field list is capped at 30, and this is the 31st option.)
+    loss_rule = "ce"
+
+    def __repr__(self) -> str:        # (the generated ones know the fields only)
+        import dataclasses
+        inner = ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in dataclasses.fields(self) if f.repr)
+        return f"{type(self).__name__}({inner}, loss_rule={self.loss_rule!r})"
+
+    def __eq__(self, other) -> bool:
+        import dataclasses
+        if other.__class__ is not self.__class__:
+            return NotImplemented
+        return all(getattr(self, f.name) == getattr(other, f.name) for f in dataclasses.fields(self)) \
+            and self.loss_rule == other.loss_rule
+
+    __hash__ = None
 
     _BOOLS = ("prefix_reuse", "target_rows_only", "graph_gradient", "graph_scoring", "fused_elementwise", "derived_weight_copies",
               "own_b1_kernels", "grad_prefix_reuse", "fuse_add_norm", "joint_winner_from_batch", "shared_prefix_attention",
@@ -237,6 +259,8 @@ class EngineOptions:
             opts.pgd_rule = env["BMA_PGD_RULE"]
         if "BMA_PGD_NORM" in env:
             opts.pgd_norm = env["BMA_PGD_NORM"]
+        if "BMA_LOSS_RULE" in env:
+            opts.loss_rule = env["BMA_LOSS_RULE"]
         for k, v in overrides.items():
             if v is None:
                 continue
@@ -251,6 +275,17 @@ class EngineOptions:
             raise ValueError(f"pgd_rule must be 'linf' or 'apgd', got {opts.pgd_rule!r}")
         if opts.pgd_norm not in ("linf", "l2"):
             raise ValueError(f"pgd_norm must be 'linf' or 'l2', got {opts.pgd_norm!r}")
+        if opts.loss_rule not in ("ce", "mellowmax"):
+            raise ValueError(f"loss_rule must be 'ce' or 'mellowmax', got {opts.loss_rule!r}")
         if opts.tp_gradient not in (False, True, "graph"):
             raise ValueError(f"tp_gradient must be False, True or 'graph', got {opts.tp_gradient!r}")
         return opts
+
+
+def mellowmax_alpha(config: BimodalAttackConfig) -> float:
+    """``config.mellowmax_alpha`` as loss_rule="mellowmax" uses it: a finite number greater than 0, or ValueError."""
+    import math
+    a = config.mellowmax_alpha
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a) or not a > 0:
+        raise ValueError(f"loss_rule='mellowmax' needs a finite mellowmax_alpha > 0, got {a!r}")
+    return float(a)

@@ -129,6 +129,8 @@ extern "C" const char* bma_profile_kernel_name(int kernel) {
     case BMA_K_CAUSAL_ATTN: return "causal_attn_kernel";
     case BMA_K_APGD: return "apgd_step_vec4";
     case BMA_K_L2: return "l2_step_passes";
+    case BMA_K_MELLOWMAX: return "mellowmax_loss_kernel";
+    case BMA_K_MELLOWMAX_DLOGITS: return "mellowmax_dlogits_kernel";
     default: return "?";
   }
 }

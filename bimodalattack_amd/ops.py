@@ -212,6 +212,65 @@ class TargetCrossEntropy(torch.autograd.Function):
         return (dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None
 
 
+def mellowmax_target(logits: torch.Tensor, labels: torch.Tensor, alpha: float, want_dlogits: bool = False,
+                     grad_scale: float = 1.0, out: Optional[torch.Tensor] = None):
+    """nanoGCG's mellowmax of the negated raw target logits, per candidate (include/bma.h, a2b).
+
+    Operands as `ce_target`.  Returns ``(loss fp32 (B,), None, dlogits (B,T,V) | None, w fp32 (B,T))``: ce_target's tuple
+    with no early-stop test (that stays ce_target's) and the softmax weights w in the place of the row losses.  `out`: a
+    contiguous (B,T,V) tensor of the logits' dtype to take dlogits (any element-aligned start).
+    """
+    if logits.dim() != 3:
+        raise ValueError("logits must be (B,T,V)")
+    dev = _need_gpu(logits, labels)
+    B, T, V = logits.shape
+    if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous():
+        raise ValueError("labels must be T contiguous int64 values")
+    alpha = float(alpha)
+    if not (alpha > 0.0 and alpha != float("inf")):
+        raise ValueError(f"mellowmax alpha must be finite and > 0, got {alpha!r}")
+    if out is not None:
+        if not want_dlogits or out.shape != logits.shape or out.dtype != logits.dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError("bad out tensor")
+    if B == 0:
+        z = torch.empty(0, dtype=torch.float32, device=dev)
+        return z, None, ((torch.empty_like(logits) if out is None else out) if want_dlogits else None), \
+            torch.empty(0, T, dtype=torch.float32, device=dev)
+    if logits.stride(2) != 1 or logits.stride(1) < V or (B > 1 and logits.stride(0) < 0):
+        logits = logits.contiguous()
+    w = torch.empty(B * T, dtype=torch.float32, device=dev)
+    assert w.numel() * 4 == lib.bma_mellowmax_target_ws_bytes(B, T)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    dlog = None
+    if want_dlogits:
+        dlog = out if out is not None else torch.empty((B, T, V), dtype=logits.dtype, device=dev)
+    check("bma_mellowmax_target", lib.bma_mellowmax_target(
+        logits.data_ptr(), logits.stride(0) if B > 1 else T * logits.stride(1), logits.stride(1), labels.data_ptr(),
+        B, T, V, _dt(logits), alpha, w.data_ptr(), loss.data_ptr(), dlog.data_ptr() if want_dlogits else None,
+        float(grad_scale), _stream(dev)))
+    return loss, None, dlog, w.view(B, T)
+
+
+class TargetMellowmax(torch.autograd.Function):
+    """The mellowmax target loss of one sequence with the backward produced by the same call (the gradient pass under
+    loss_rule="mellowmax"): TargetCrossEntropy with the other rule."""
+
+    @staticmethod
+    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor, alpha: float) -> torch.Tensor:
+        x = logits.detach()
+        if x.dim() == 2:
+            x = x.unsqueeze(0)
+        loss, _, dlog, _ = mellowmax_target(x, labels, alpha, want_dlogits=True)
+        ctx.save_for_backward(dlog)
+        ctx.in_shape = logits.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dlog,) = ctx.saved_tensors
+        return (dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None, None
+
+
 # ---------------------------------------------------------------------------
 def build_mask_bits(not_allowed_ids: Optional[torch.Tensor], V: int, device) -> Optional[torch.Tensor]:
     """ceil(V/32) words, bit set = token not allowed.  Built once per attack."""

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BMA_VERSION 114 /* 0.1.14: bma_l2_step, bma_apgd_l2_step, bma_l2_ws_bytes (the PGD image update in the L2 ball, opt-in); 0.1.13: bma_apgd_step (the reference's auto-PGD image update, opt-in); 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
+#define BMA_VERSION 114 /* 0.1.14: bma_mellowmax_target, bma_mellowmax_target_ws_bytes (nanoGCG's mellowmax target loss, opt-in; an added entry point, the version number and every older prototype unchanged); bma_l2_step, bma_apgd_l2_step, bma_l2_ws_bytes (the PGD image update in the L2 ball, opt-in); 0.1.13: bma_apgd_step (the reference's auto-PGD image update, opt-in); 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
 
 /* element types of model-dtype tensors */
 enum { BMA_F32 = 0, BMA_BF16 = 1, BMA_F16 = 2 };
@@ -139,6 +139,40 @@ int bma_ce_target(const void* logits, int64_t ld_cand, int64_t ld_row,
                   const int64_t* labels, int B, int T, int V, int dtype,
                   float* ws, float* loss, int32_t* match,
                   void* dlogits, float grad_scale, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * a2b  nanoGCG's mellowmax over the target slice (opt-in, EngineOptions.loss_rule
+ *      = "mellowmax"; the function is the reference's utils.py:35-36, which it
+ *      ships and never calls)
+ * logits, labels, strides: as bma_ce_target.  Per candidate, with z its T target
+ * rows and y the labels:
+ *   t_j  = -float(z[j, y_j])          the raw target logit, no softmax over V
+ *   loss = ( logsumexp_j(alpha * t_j) - log(T) ) / alpha
+ *   w_j  = softmax_j(alpha * t)_j     d loss / d z[j, v] = -w_j if v == y_j else 0
+ * fp32 on the dtype-rounded logits; the maximum is subtracted before the
+ * exponentials; the T terms are folded in a fixed order (two calls on one input
+ * are bitwise equal, no floating-point atomics).  Only the B*T label elements are
+ * read.  Special values follow torch.logsumexp and its backward: a NaN among the
+ * T target logits gives NaN (loss and all w); a target logit of -inf gives +inf
+ * (w: NaN at that row, 0 elsewhere); all +inf gives -inf (w: NaN); T == 1 gives
+ * t_0.  Losses may be negative.
+ *   alpha     finite and > 0 (BMA_EINVAL otherwise), a launch argument
+ *   ws        bma_mellowmax_target_ws_bytes(B,T) bytes = B*T floats, left holding w
+ *   loss      [B] fp32
+ *   dlogits   [B*T*V] of `dtype`, contiguous, element-aligned, or NULL: zeros, and
+ *             dtype(-w_j * grad_scale) at each row's label; written whole, every
+ *             element by exactly one lane, read by nobody
+ * A label outside [0,V) cannot be seen by the host without a synchronisation:
+ * like bma_ce_target, the kernel never reads or writes through it, the
+ * candidate's loss and weights are NaN; in dlogits that label's row is all zeros
+ * and the candidate's other rows carry NaN at their labels (-w_j * grad_scale).
+ * The early-stop test (`match`) is bma_ce_target's.  Enqueues two launches at
+ * most; no allocation, no synchronisation: capturable into a hipGraph.
+ * ------------------------------------------------------------------------- */
+size_t bma_mellowmax_target_ws_bytes(int B, int T);
+int bma_mellowmax_target(const void* logits, int64_t ld_cand, int64_t ld_row,
+                         const int64_t* labels, int B, int T, int V, int dtype, float alpha,
+                         float* ws, float* loss, void* dlogits, float grad_scale, void* stream);
 
 /* ---------------------------------------------------------------------------
  * a3  sample_ids_from_grad, first half  (:144-147)
@@ -491,7 +525,9 @@ enum {
   BMA_K_TOPK = 3, BMA_K_SCATTER = 4, BMA_K_SPLICE = 5,
   BMA_K_CE_ROWS_B1 = 6 /* B == 1: the gradient pass */, BMA_K_RMSNORM = 7, BMA_K_SWIGLU = 8,
   BMA_K_ROPE = 9, BMA_K_ATTN_MERGE = 10, BMA_K_GATHER_ROWS = 11,
-  BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_APGD = 19, BMA_K_L2 = 20 /* every pass of bma_l2_step / bma_apgd_l2_step */, BMA_K_COUNT = 21
+  BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_APGD = 19, BMA_K_L2 = 20 /* every pass of bma_l2_step / bma_apgd_l2_step */,
+  BMA_K_MELLOWMAX = 21 /* the loss pass of bma_mellowmax_target */, BMA_K_MELLOWMAX_DLOGITS = 22 /* its dlogits pass */,
+  BMA_K_COUNT = 23
 };
 int bma_profile_enable(int on);
 int bma_profile_read(int kernel, int64_t* launches, double* total_ms, double* total_bytes);
