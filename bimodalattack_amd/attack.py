@@ -298,6 +298,10 @@ class BimodalAttack:
         self._mm_alpha = mellowmax_alpha(config) if self.opt.loss_rule == "mellowmax" else None
         if self._mm_alpha is not None:
             logger.info(f"Target loss: mellowmax, alpha = {self._mm_alpha} (loss_rule; the default is the cross-entropy)")
+        # loss_rule "margin": kappa comes with the options (checked by from_env)
+        self._margin_kappa = float(self.opt.margin_kappa) if self.opt.loss_rule == "margin" else None
+        if self._margin_kappa is not None:
+            logger.info(f"Target loss: margin, kappa = {self._margin_kappa} (loss_rule; the default is the cross-entropy)")
         if model.device.type != "cuda":
             raise RuntimeError(
                 f"bimodalattack_amd runs on an AMD GPU only (model is on {model.device}); there is no CPU path. "
@@ -572,8 +576,14 @@ class BimodalAttack:
     def _target_loss(self, logits: Tensor, scoring: bool = False):
         """The target loss by EngineOptions.loss_rule.  Gradient pass: the (T, V) target rows of the one sequence -> the scalar
         loss, differentiable (the kernel's own dlogits).  scoring=True: (B, T, V) -> (loss (B,) fp32, early-stop hit or
-        None); the hit is the argmax test of the cross-entropy kernel's row pass under either rule."""
+        None); the hit is the argmax test of the cross-entropy kernel's row pass under "ce" and "mellowmax"; the margin's
+        own row pass finds each row's top-1 and returns the same test from its one read of the logits."""
         mm, want_hit = self._mm_alpha is not None, bool(scoring and self.config.early_stop)
+        if self._margin_kappa is not None:
+            if not scoring:
+                return ops.TargetMargin.apply(logits, self.labels, self._margin_kappa)
+            loss, hit, _, _ = ops.margin_target(logits, self.labels, self._margin_kappa, want_match=want_hit)
+            return loss, hit
         if not scoring:
             return (ops.TargetMellowmax.apply(logits, self.labels, self._mm_alpha) if mm
                     else ops.TargetCrossEntropy.apply(logits, self.labels))

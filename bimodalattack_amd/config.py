@@ -75,7 +75,7 @@ class EngineOptions:
     """Knobs of the MI355X engine that the reference has no field for: the ones a test or bench.py flips.
 
     Read from keyword arguments of :func:`bimodalattack_amd.run` or from the environment (``BMA_<NAME>``), never from
-    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule``, ``pgd_norm`` and ``loss_rule`` only changes speed (tests/test_attack_gpu.py runs the reference's golden
+    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule``, ``pgd_norm`` and ``loss_rule`` (with ``margin_kappa``) only changes speed (tests/test_attack_gpu.py runs the reference's golden
     trajectories with each restructuring off).  Finer switches that exist for A/B measurements only are module constants
     read from the environment once (round 5: 42 options -> 27): ``ops.OWN_KERNELS`` (each hand-written batch-1 kernel),
     ``attack.MASKLESS_B1_ATTENTION`` / ``CHUNK_QUANTUM`` / ``EMULATE_WORLD``, ``fused.FUSE_QK_ROPE``,
@@ -194,19 +194,27 @@ class EngineOptions:
     # `config.use_mellowmax` does NOT select it: the dataclass behaves as the reference's, which ignores that field.
     # (Set like every option -- keyword of run() / from_env, or BMA_LOSS_RULE -- but a plain attribute, not a dataclass
     # field: the field list is capped at 30, and this is the 31st option.)
+    # "margin" = the Carlini-Wagner margin of the adversarial-robustness literature (Faster-GCG's loss, auto-PGD's
+    # companion): per target row the best wrong logit minus the target logit, clamped below at -margin_kappa, averaged
+    # over the rows (csrc/margin_target.hip, contract in include/bma.h a2c).  A row whose margin is below -kappa is won
+    # and stops pulling; with kappa = 0 every margin < 0 means the early-stop test holds.  The same read of the logits
+    # gives early_stop's argmax test, so the rule never runs the cross-entropy kernel.
     loss_rule = "ce"
+    # kappa of loss_rule="margin" (unread otherwise): a real number >= 0, +inf = no clamp.  A plain attribute like
+    # loss_rule (keyword of run() / from_env, or BMA_MARGIN_KAPPA).
+    margin_kappa = 0.0
 
     def __repr__(self) -> str:        # (the generated ones know the fields only)
         import dataclasses
         inner = ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in dataclasses.fields(self) if f.repr)
-        return f"{type(self).__name__}({inner}, loss_rule={self.loss_rule!r})"
+        return f"{type(self).__name__}({inner}, loss_rule={self.loss_rule!r}, margin_kappa={self.margin_kappa!r})"
 
     def __eq__(self, other) -> bool:
         import dataclasses
         if other.__class__ is not self.__class__:
             return NotImplemented
         return all(getattr(self, f.name) == getattr(other, f.name) for f in dataclasses.fields(self)) \
-            and self.loss_rule == other.loss_rule
+            and self.loss_rule == other.loss_rule and self.margin_kappa == other.margin_kappa
 
     __hash__ = None
 
@@ -261,6 +269,11 @@ class EngineOptions:
             opts.pgd_norm = env["BMA_PGD_NORM"]
         if "BMA_LOSS_RULE" in env:
             opts.loss_rule = env["BMA_LOSS_RULE"]
+        if "BMA_MARGIN_KAPPA" in env:
+            try:
+                opts.margin_kappa = float(env["BMA_MARGIN_KAPPA"])
+            except ValueError:
+                raise ValueError(f"margin_kappa (BMA_MARGIN_KAPPA) must be a number >= 0, got {env['BMA_MARGIN_KAPPA']!r}") from None
         for k, v in overrides.items():
             if v is None:
                 continue
@@ -275,8 +288,12 @@ class EngineOptions:
             raise ValueError(f"pgd_rule must be 'linf' or 'apgd', got {opts.pgd_rule!r}")
         if opts.pgd_norm not in ("linf", "l2"):
             raise ValueError(f"pgd_norm must be 'linf' or 'l2', got {opts.pgd_norm!r}")
-        if opts.loss_rule not in ("ce", "mellowmax"):
-            raise ValueError(f"loss_rule must be 'ce' or 'mellowmax', got {opts.loss_rule!r}")
+        if opts.loss_rule not in ("ce", "mellowmax", "margin"):
+            raise ValueError(f"loss_rule must be 'ce', 'mellowmax' or 'margin', got {opts.loss_rule!r}")
+        k = opts.margin_kappa
+        if isinstance(k, bool) or not isinstance(k, (int, float)) or not k >= 0:      # NaN fails the comparison
+            raise ValueError(f"margin_kappa must be a real number >= 0 (+inf: no clamp), got {k!r}")
+        opts.margin_kappa = float(k)
         if opts.tp_gradient not in (False, True, "graph"):
             raise ValueError(f"tp_gradient must be False, True or 'graph', got {opts.tp_gradient!r}")
         return opts

@@ -131,6 +131,8 @@ extern "C" const char* bma_profile_kernel_name(int kernel) {
     case BMA_K_L2: return "l2_step_passes";
     case BMA_K_MELLOWMAX: return "mellowmax_loss_kernel";
     case BMA_K_MELLOWMAX_DLOGITS: return "mellowmax_dlogits_kernel";
+    case BMA_K_MARGIN: return "margin_rows_kernel";
+    case BMA_K_MARGIN_DLOGITS: return "margin_dlogits_kernel";
     default: return "?";
   }
 }

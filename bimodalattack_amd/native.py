@@ -58,6 +58,9 @@ PROTOTYPES = {
     "bma_mellowmax_target_ws_bytes": (c_size_t, [c_int, c_int]),
     "bma_mellowmax_target": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                      c_void_p, c_void_p, c_float, c_void_p]),
+    "bma_margin_target_ws_bytes": (c_size_t, [c_int, c_int]),
+    "bma_margin_target": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "bma_mask_topk_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bma_mask_topk": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "bma_rand_positions": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -141,7 +144,8 @@ PROTOTYPES = {
 KERNEL_IDS = {"linf": 0, "ce_rows": 1, "ce_dlogits": 2, "mask_topk": 3, "sample_scatter": 4, "splice": 5,
               "ce_rows_grad": 6, "rmsnorm": 7, "swiglu": 8, "rope": 9, "attn_merge": 10, "gather_rows": 11,
               "ragged_attn": 12, "prefix_attn": 13, "add_rmsnorm": 14, "gemm_nt": 15, "b1_attn": 16, "gemm_mid": 17, "causal_attn": 18,
-              "apgd": 19, "l2": 20, "mellowmax": 21, "mellowmax_dlogits": 22}
+              "apgd": 19, "l2": 20, "mellowmax": 21, "mellowmax_dlogits": 22,
+              "margin": 23, "margin_dlogits": 24}
 
 
 def profile_enable(on: bool) -> None:

@@ -271,6 +271,71 @@ class TargetMellowmax(torch.autograd.Function):
         return (dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None, None
 
 
+def margin_target(logits: torch.Tensor, labels: torch.Tensor, kappa: float, want_match: bool = False,
+                  want_dlogits: bool = False, grad_scale: float = 1.0, out: Optional[torch.Tensor] = None):
+    """The Carlini-Wagner margin between the best wrong logit and the target logit, clamped at -kappa and averaged over
+    the target rows, per candidate (include/bma.h, a2c).
+
+    Operands as `ce_target`.  Returns ``(loss fp32 (B,), match int32 (B,) | None, dlogits (B,T,V) | None, m fp32 (B,T))``:
+    ce_target's tuple with the unclamped row margins m in the place of the row losses; `match` is ce_target's early-stop
+    test, from the same read of the logits.  `out`: a contiguous (B,T,V) tensor of the logits' dtype to take dlogits (any
+    element-aligned start).
+    """
+    if logits.dim() != 3:
+        raise ValueError("logits must be (B,T,V)")
+    dev = _need_gpu(logits, labels)
+    B, T, V = logits.shape
+    if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous():
+        raise ValueError("labels must be T contiguous int64 values")
+    kappa = float(kappa)
+    if not kappa >= 0.0:
+        raise ValueError(f"margin kappa must be >= 0 (+inf: no clamp), got {kappa!r}")
+    if V < 2:
+        raise ValueError("the margin needs V >= 2: there is no wrong logit")
+    if out is not None:
+        if not want_dlogits or out.shape != logits.shape or out.dtype != logits.dtype or out.device != dev or not out.is_contiguous():
+            raise ValueError("bad out tensor")
+    if B == 0:
+        z = torch.empty(0, dtype=torch.float32, device=dev)
+        return z, (torch.empty(0, dtype=torch.int32, device=dev) if want_match else None), \
+            ((torch.empty_like(logits) if out is None else out) if want_dlogits else None), \
+            torch.empty(0, T, dtype=torch.float32, device=dev)
+    if logits.stride(2) != 1 or logits.stride(1) < V or (B > 1 and logits.stride(0) < 0):
+        logits = logits.contiguous()
+    ws = torch.empty(3 * B * T, dtype=torch.float32, device=dev)
+    assert ws.numel() * 4 == lib.bma_margin_target_ws_bytes(B, T)
+    loss = torch.empty(B, dtype=torch.float32, device=dev)
+    match = torch.empty(B, dtype=torch.int32, device=dev) if want_match else None
+    dlog = None
+    if want_dlogits:
+        dlog = out if out is not None else torch.empty((B, T, V), dtype=logits.dtype, device=dev)
+    check("bma_margin_target", lib.bma_margin_target(
+        logits.data_ptr(), logits.stride(0) if B > 1 else T * logits.stride(1), logits.stride(1), labels.data_ptr(),
+        B, T, V, _dt(logits), kappa, ws.data_ptr(), loss.data_ptr(), match.data_ptr() if want_match else None,
+        dlog.data_ptr() if want_dlogits else None, float(grad_scale), _stream(dev)))
+    return loss, match, dlog, ws[: B * T].view(B, T)
+
+
+class TargetMargin(torch.autograd.Function):
+    """The margin target loss of one sequence with the backward produced by the same call (the gradient pass under
+    loss_rule="margin"): TargetCrossEntropy with the other rule."""
+
+    @staticmethod
+    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor, kappa: float) -> torch.Tensor:
+        x = logits.detach()
+        if x.dim() == 2:
+            x = x.unsqueeze(0)
+        loss, _, dlog, _ = margin_target(x, labels, kappa, want_dlogits=True)
+        ctx.save_for_backward(dlog)
+        ctx.in_shape = logits.shape
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dlog,) = ctx.saved_tensors
+        return (dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None, None
+
+
 # ---------------------------------------------------------------------------
 def build_mask_bits(not_allowed_ids: Optional[torch.Tensor], V: int, device) -> Optional[torch.Tensor]:
     """ceil(V/32) words, bit set = token not allowed.  Built once per attack."""

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BMA_VERSION 114 /* 0.1.14: bma_mellowmax_target, bma_mellowmax_target_ws_bytes (nanoGCG's mellowmax target loss, opt-in; an added entry point, the version number and every older prototype unchanged); bma_l2_step, bma_apgd_l2_step, bma_l2_ws_bytes (the PGD image update in the L2 ball, opt-in); 0.1.13: bma_apgd_step (the reference's auto-PGD image update, opt-in); 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
+#define BMA_VERSION 114 /* 0.1.14: bma_margin_target, bma_margin_target_ws_bytes (the Carlini-Wagner margin target loss, opt-in; added entry points, the version number and every older prototype unchanged); bma_mellowmax_target, bma_mellowmax_target_ws_bytes (nanoGCG's mellowmax target loss, opt-in; an added entry point, the version number and every older prototype unchanged); bma_l2_step, bma_apgd_l2_step, bma_l2_ws_bytes (the PGD image update in the L2 ball, opt-in); 0.1.13: bma_apgd_step (the reference's auto-PGD image update, opt-in); 0.1.12: bma_prefix_attention_set_plan (128-wide heads on the 32x32x16 kernel: 64-key chunks by LDS-DMA); 0.1.11: bma_causal_attention_gqa(+_bwd_gqa) (grouped-query heads, 256-wide heads: Gemma-3's decoder at batch 1); 0.1.10: bma_add_layernorm(+_bwd) (CLIP's residual add + LayerNorm pairs in one launch each way); 0.1.9: bma_gemm_nt_next (cross-product weight prefetch), bma_gemm_nt_set_plan flags bit 3 (fenced split-K hand-off); 0.1.8: bma_causal_attention(+_bwd) (one long sequence at batch 1); 0.1.7: bma_gemm_mid (the 599-644-row products of the pass with the image in the prompt); 0.1.6: bma_b1_attention(+_bwd); bma_gemm_nt_plan / _set_plan (slab height chosen with the split count); 0.1.5: bma_quick_gelu(+_bwd); 0.1.4: bma_qknorm_rope2; 0.1.3: bma_allgather_f32; 0.1.2: bma_add_rmsnorm(+_bwd), bma_rope2, bma_splice_rows, bma_gemm_nt; 0.1.1: bma_mask_topk takes a workspace; bma_ragged_attention takes blocks of any length, 256-wide heads */
 
 /* element types of model-dtype tensors */
 enum { BMA_F32 = 0, BMA_BF16 = 1, BMA_F16 = 2 };
@@ -173,6 +173,53 @@ size_t bma_mellowmax_target_ws_bytes(int B, int T);
 int bma_mellowmax_target(const void* logits, int64_t ld_cand, int64_t ld_row,
                          const int64_t* labels, int B, int T, int V, int dtype, float alpha,
                          float* ws, float* loss, void* dlogits, float grad_scale, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * a2c  the Carlini-Wagner margin over the target slice (opt-in,
+ *      EngineOptions.loss_rule = "margin")
+ * logits, labels, strides: as bma_ce_target.  Per candidate b and target row j
+ * with label y_j; z = float(logits[b, j, :]), the dtype-rounded logits widened
+ * to fp32:
+ *   o_j    = max over v != y_j of z_v
+ *   i_j    = the FIRST index v != y_j with z_v == o_j        (o_j is z[i_j])
+ *   m_j    = o_j - z[y_j]                       one fp32 subtraction
+ *   l_j    = max(m_j, -kappa)
+ *   loss_b = (sum_j l_j) / T                    fp32, summed in row order: two calls
+ *                                               on one input are bitwise equal, no
+ *                                               floating-point atomics
+ *   a_j    = 1 if m_j >= -kappa else 0          torch.clamp's backward: equality
+ *                                               passes, NaN does not
+ *   g      = grad_scale / (float)T              one fp32 division
+ *   dlogits[b,j,y_j] = dtype(-g), dlogits[b,j,i_j] = dtype(+g) where a_j = 1;
+ *                      every other element, and every element of a row with
+ *                      a_j = 0, is +0
+ *   match_b = bma_ce_target's early-stop test, bit for bit: on every row the
+ *             first argmax over ALL v (NaN skipped) equals y_j
+ * m_j < 0 on every row implies match_b, and match_b implies m_j <= 0 on every
+ * row; m_j == 0 is a tie, which the lower index wins.
+ * Special values follow IEEE arithmetic and the comparisons as written: a NaN
+ * anywhere in a row (the label's element included) gives m_j = NaN, the
+ * candidate's loss is NaN and that row of dlogits is all zeros; z[y_j] = -inf
+ * beside a finite o_j gives m_j = +inf, an active row; a row that is all -inf
+ * gives NaN (i_j is still its first index v != y_j); maxima start from
+ * -INFINITY.  A label outside [0,V) is never read or written through: m_j =
+ * NaN, the candidate's loss is NaN and its match 0, that row of dlogits is
+ * zeros, the candidate's other rows are written normally.
+ *   kappa     >= 0, +inf allowed (no clamp); NaN or negative: BMA_EINVAL
+ *   V         >= 2 (BMA_EINVAL below: there is no wrong logit)
+ *   ws        bma_margin_target_ws_bytes(B,T) bytes = 3*B*T 4-byte words, left
+ *             holding m f32 | i int32 (-1: every v != y_j is NaN) | row hit int32
+ *   loss      [B] fp32;  match [B] int32 or NULL
+ *   dlogits   [B*T*V] of `dtype`, contiguous, element-aligned, or NULL; written
+ *             whole, every element by exactly one lane, read by nobody
+ * All V columns of all B*T rows are read exactly once.  Enqueues three launches
+ * at most; no allocation, no synchronisation: capturable into a hipGraph.
+ * ------------------------------------------------------------------------- */
+size_t bma_margin_target_ws_bytes(int B, int T);
+int bma_margin_target(const void* logits, int64_t ld_cand, int64_t ld_row,
+                      const int64_t* labels, int B, int T, int V, int dtype, float kappa,
+                      float* ws, float* loss, int32_t* match, void* dlogits,
+                      float grad_scale, void* stream);
 
 /* ---------------------------------------------------------------------------
  * a3  sample_ids_from_grad, first half  (:144-147)
@@ -527,7 +574,8 @@ enum {
   BMA_K_ROPE = 9, BMA_K_ATTN_MERGE = 10, BMA_K_GATHER_ROWS = 11,
   BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_APGD = 19, BMA_K_L2 = 20 /* every pass of bma_l2_step / bma_apgd_l2_step */,
   BMA_K_MELLOWMAX = 21 /* the loss pass of bma_mellowmax_target */, BMA_K_MELLOWMAX_DLOGITS = 22 /* its dlogits pass */,
-  BMA_K_COUNT = 23
+  BMA_K_MARGIN = 23 /* the row pass of bma_margin_target */, BMA_K_MARGIN_DLOGITS = 24 /* its dlogits pass */,
+  BMA_K_COUNT = 25
 };
 int bma_profile_enable(int on);
 int bma_profile_read(int kernel, int64_t* launches, double* total_ms, double* total_bytes);

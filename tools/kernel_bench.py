@@ -50,6 +50,14 @@ def cases():
         out = torch.empty_like(x) if grad else None
         return lambda: ops.mellowmax_target(x, lab, 1.0, want_dlogits=grad, out=out)
 
+    def margin(B, T, V, grad):
+        # the row pass streams all B*T*V elements (ce_rows' bytes); grad: the write-only dlogits pass after it, which has a
+        # profile slot of its own and is what the case reports
+        x = (torch.randn((B, T, V), generator=g, device=DEV) * 2).to(bf)
+        lab = torch.randint(0, V, (T,), generator=g, device=DEV)
+        out = torch.empty_like(x) if grad else None
+        return lambda: ops.margin_target(x, lab, 0.0, want_match=True, want_dlogits=grad, out=out)
+
     def splice(B, lens, D, V=32064, n_opt=19):
         table = torch.randn((V, D), generator=g, device=DEV).to(bf)
         ids = torch.randint(0, V, (B, n_opt), generator=g, device=DEV)
@@ -316,9 +324,13 @@ def cases():
         "ce_rows/llava_B512_T20_V32064": ("ce_rows", lambda: ce(512, 20, 32064)),
         "ce_rows/llava_B64_T20_V32064": ("ce_rows", lambda: ce(64, 20, 32064)),
         "ce_rows/gemma_B64_T20_V262208": ("ce_rows", lambda: ce(64, 20, 262208)),
+        "ce_rows/gemma_B128_T20_V262208": ("ce_rows", lambda: ce(128, 20, 262208)),
         "ce_dlogits/llava_T20_V32064": ("ce_dlogits", lambda: ce_grad(20, 32064)),
         "mellowmax/loss_B512_T20_V32064": ("mellowmax", lambda: mellowmax(512, 20, 32064, False)),
         "mellowmax/dlogits_B512_T20_V32064": ("mellowmax_dlogits", lambda: mellowmax(512, 20, 32064, True)),
+        "margin/loss_B512_T20_V32064": ("margin", lambda: margin(512, 20, 32064, False)),
+        "margin/dlogits_B512_T20_V32064": ("margin_dlogits", lambda: margin(512, 20, 32064, True)),
+        "margin/loss_B128_T20_V262208": ("margin", lambda: margin(128, 20, 262208, False)),
         "splice/c3_tail_B512_S44_D4096": ("splice", lambda: splice(512, ["g", 6, 19], 4096)),
         "splice/c3_full_B512_S65_D4096": ("splice", lambda: splice(512, [21, "g", 6, 19], 4096)),
         "splice/c4_full_B64_S643_D4096": ("splice", lambda: splice(64, [5, 576, 18, "g", 6, 19], 4096)),
