@@ -86,6 +86,16 @@ __device__ __forceinline__ uint4_t pack8(const float (&v)[8]) {
   return w;
 }
 
+// one element of the rotation, bma_rope2's arithmetic: dt(dt(x cos) + dt(sign x' sin)).  Contraction is off here as it is
+// in fused_elementwise.hip: with it on, LLVM narrows the f16 form to half-precision mul + add and fuses them into an FMA,
+// which drops the rounding of x cos -- the f16 kernels then rotate q, k, dq and dk differently from bma_rope2 by an ulp in
+// some elements (tests/test_attention_grad_gpu.py: the lse of a one-token f16 sequence was 49 bounds off).
+template <int DT>
+__device__ __forceinline__ float rope_one(float x, float p, float c, float s, float sign) {
+#pragma clang fp contract(off)
+  return rnd<DT>(rnd<DT>(x * c) + rnd<DT>(sign * p * s));
+}
+
 // chunk c (8 elements) of a head vector after the rotation, bma_rope2's arithmetic: o = dt(dt(x cos) + dt(+-x' sin)),
 // x' the element 64 away, minus for the first half (rotate_half = cat(-x2, x1)); sin_sign = -1 gives the inverse
 template <int DT>
@@ -98,7 +108,7 @@ __device__ __forceinline__ void rope_chunk(const char* head, const char* cosrow,
   unpack8<DT>(*reinterpret_cast<const uint4_t*>(sinrow + c * 16), sf);
   const float sign = (c < 8 ? -1.0f : 1.0f) * sin_sign;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = rnd<DT>(rnd<DT>(x[j] * cf[j]) + rnd<DT>(sign * p[j] * sf[j]));
+  for (int j = 0; j < 8; ++j) o[j] = rope_one<DT>(x[j], p[j], cf[j], sf[j], sign);
 }
 
 // the same from chunks already in registers (x: the chunk, p: its partner 64 elements away)
@@ -111,7 +121,7 @@ __device__ __forceinline__ uint4_t rope_regs(const uint4_t& xw, const uint4_t& p
   unpack8<DT>(sw, sf);
   const float sign = c < 8 ? -1.0f : 1.0f;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) o[j] = rnd<DT>(rnd<DT>(x[j] * cf[j]) + rnd<DT>(sign * p[j] * sf[j]));
+  for (int j = 0; j < 8; ++j) o[j] = rope_one<DT>(x[j], p[j], cf[j], sf[j], sign);
   return pack8<DT>(o);
 }
 
@@ -476,7 +486,7 @@ __global__ __launch_bounds__(kNT) void b1_attn_bwd_kernel(Args a) {
         const float sf[4] = {bma::unpack16<DT>(sw.x, 0), bma::unpack16<DT>(sw.x, 1), bma::unpack16<DT>(sw.y, 0), bma::unpack16<DT>(sw.y, 1)};
         const float sign = dt < 4 ? 1.0f : -1.0f;              // -(rotate_half's sign)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = rnd<DT>(rnd<DT>(o[e] * cf[e]) + rnd<DT>(sign * p[e] * sf[e]));
+        for (int e = 0; e < 4; ++e) o[e] = rope_one<DT>(o[e], p[e], cf[e], sf[e], sign);
       }
       bma::uint2_t w;
       w.x = bma::pack16<DT>(o[0], o[1]);

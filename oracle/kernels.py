@@ -556,3 +556,218 @@ def gated_bwd_ratios(dg, du, gate, up, dy, act, dt):
     lo, hi, amb = d_up_interval(gate, dy, act, a64, dt)
     ru = ((f64(du) - 0.5 * (lo + hi)).abs() / (0.5 * (hi - lo))).max().item()
     return rg, ru, amb.double().mean().item()
+
+
+# --------------------------------------------------------------------------
+# gradient-pass attention (csrc/causal_attention.hip: causal_fwd/dq/dkv_kernel; csrc/b1_attention.hip)
+# --------------------------------------------------------------------------
+# No reference program: attention and its backward in float64 on the 16-bit operands, and per ELEMENT the error a correct
+# flash evaluation keeps.  The kernels round P and dS to the 16-bit type before their products and read delta from the
+# rounded output; each of those roundings is relative to one term of a sum, so what one output element collects is
+# u times the sum of the terms' sizes -- B below -- and, where a term falls into the type's subnormal range (fp16: P and
+# dS of far keys), half a subnormal spacing per visible term -- Z.  A whole-tensor maximum would be set by the late
+# queries and early keys, whose sums are long; these bounds shrink with the row.  Used by tests/test_attention_refs.py
+# (CPU: against autograd, a restatement of the kernels, and mutants of it) and tests/test_attention_grad_gpu.py.
+LOG2E = 1.4426950408889634
+AttnRef = namedtuple("AttnRef", "o lse2 dq dk dv B Z")
+
+# ATTN_C: the correct fp32 restatements of the kernels (tests/test_attention_refs.py: restate_causal, restate_b1) reach
+# at most ATTN_WORST of the bound at C = 1 over every case of attention_cases(), ATTN_TWO_TILE_CASES and B1_S x B1_H, both
+# dtypes, all input families; C is the smallest power of two >= 2 * that.  The factor of two is for what the restatements
+# leave out: the order of the fp32 accumulation inside the matrix cores, v_exp_f32 / v_log_f32 being accurate to about
+# an ulp.  Measured per output at C = 1 -- causal: o 0.83, dq 0.50, dk 0.94, dv 0.97; b1: o 0.94, dqkv 0.993 (a dv of the last key: one term, its P rounded, then the result).
+# ATTN_C_LSE the same for the log-sum-exp against 2^-24 * max(1, |ref|), from ATTN_LSE_WORST (causal 26.3, b1 16.4: sharp
+# fp16 rows of two or three keys whose lse2 is below one while sum |q_d k_d| scale log2(e) is about 40 -- the fp32 dot
+# product's own error, relative to a result that cancelled).
+ATTN_WORST = 0.993
+ATTN_C = 2
+ATTN_LSE_WORST = 26.3
+ATTN_C_LSE = 64
+
+
+def _visible(Lq, Lk, causal, device=None):
+    """(Lq, Lk) bool: the queries are the LAST Lq positions, query i sees keys 0 .. Lk - Lq + i."""
+    if not causal:
+        return torch.ones((Lq, Lk), dtype=torch.bool, device=device)
+    return torch.arange(Lk, device=device)[None, :] <= (Lk - Lq + torch.arange(Lq, device=device))[:, None]
+
+
+def attention_ref(q, k, v, d_out, scale, causal, dt) -> AttnRef:
+    """Attention of q (Lq,H,Dh) -- the last Lq positions -- over k / v (Lk,Hkv,Dh), query head h reading key/value head
+    h // rep, and its backward for d_out (Lq,H,Dh), in float64 on operands already rounded to `dt`.  o, dq (Lq,H,Dh);
+    dk, dv (Lk,Hkv,Dh) summed over the group; lse2 (H,Lq) = log2 of the denominator of the scaled scores.  B[name] and
+    Z[name], shaped like the output: with p the probabilities, dP = dO.V^T and dabs_i = sum_d |dO_id||o_id| (what an
+    error in the rounded o does to delta_i; |delta_i| itself would miss it, the sum over d cancels),
+    A = p o (|dP| + dabs):   o: p.|v|   dv: p^T.|dO|   dq: scale A.|k|   dk: scale A^T.|q|;   Z the same with the 0/1
+    visibility mask in place of p."""
+    q, k, v, do = f64(q), f64(k), f64(v), f64(d_out)
+    assert all(torch.equal(round_dt(t, dt), t) for t in (q, k, v, do)), "the operands must be values of dt"
+    (Lq, H, Dh), (Lk, Hkv, _) = q.shape, k.shape
+    rep = H // Hkv
+    scale = float(np.float32(scale))                       # as the fp32 number the C entry point gets
+    ke, ve = k.repeat_interleave(rep, 1), v.repeat_interleave(rep, 1)
+    vis = _visible(Lq, Lk, causal, q.device)
+    s = (torch.einsum("qhd,khd->hqk", q, ke) * scale).masked_fill(~vis[None], float("-inf"))
+    lse = torch.logsumexp(s, -1)
+    p = torch.exp(s - lse[..., None])
+    o = torch.einsum("hqk,khd->qhd", p, ve)
+    dP = torch.einsum("qhd,khd->hqk", do, ve)
+    delta = (do * o).sum(-1).t()[..., None]
+    dS = p * (dP - delta) * scale
+    group = lambda t: t.view(Lk, Hkv, rep, Dh).sum(2)      # noqa: E731
+    dq = torch.einsum("hqk,khd->qhd", dS, ke)
+    dk = group(torch.einsum("hqk,qhd->khd", dS, q))
+    dv = group(torch.einsum("hqk,qhd->khd", p, do))
+    mag = dP.abs() + (do.abs() * o.abs()).sum(-1).t()[..., None]
+    B, Z = {}, {}
+    for out, w in ((B, p), (Z, vis[None].to(torch.float64).expand_as(p))):
+        a = w * mag * scale
+        out["o"] = torch.einsum("hqk,khd->qhd", w, ve.abs())
+        out["dv"] = group(torch.einsum("hqk,qhd->khd", w, do.abs()))
+        out["dq"] = torch.einsum("hqk,khd->qhd", a, ke.abs())
+        out["dk"] = group(torch.einsum("hqk,qhd->khd", a, q.abs()))
+    return AttnRef(o, lse * LOG2E, dq, dk, dv, B, Z)
+
+
+def attention_tol(ref: AttnRef, name, dt):
+    """Largest |got - ref| a correct kernel leaves in output `name`, per element: ATTN_C roundings of the terms it sums
+    (with their subnormal floors), and the one rounding of the result with its floor."""
+    u, eta = unit_roundoff(dt), half_subnormal(dt)
+    return ATTN_C * (u * ref.B[name] + eta * ref.Z[name]) + u * getattr(ref, name).abs() + eta
+
+
+def lse_tol(ref_lse):
+    return ATTN_C_LSE * U32 * ref_lse.abs().clamp_min(1.0)
+
+
+def _worst(err, tol):
+    r = err / tol
+    i = int(r.argmax())
+    return r.flatten()[i].item(), tuple(int(j) for j in np.unravel_index(i, tuple(r.shape)))
+
+
+def attention_ratios(got, ref: AttnRef, dt):
+    """{name: (worst |got - ref| / bound, the element where it occurs)} for the outputs given in the dict `got`
+    (o, dq: (row, head, dim); dk, dv: (key, key/value head, dim); lse2: (head, row)): every check is `<= 1`.  A
+    non-finite result counts as infinitely wrong."""
+    out = {}
+    for name, g in got.items():
+        want = getattr(ref, name)
+        err = torch.nan_to_num((f64(g).to(want.device) - want).abs(), nan=float("inf"))
+        out[name] = _worst(err, lse_tol(want) if name == "lse2" else attention_tol(ref, name, dt))
+    return out
+
+
+B1Ref = namedtuple("B1Ref", "o lse dqkv tol_o tol_dqkv")
+
+
+def _rot_partner(t):
+    h = t.shape[-1] // 2
+    return torch.cat([t[..., h:], t[..., :h]], -1)
+
+
+def b1_attention_ref(qkv, cos, sin, H, scale, d_out, dt) -> B1Ref:
+    """bma_b1_attention and its backward: qkv (S, 3*H*Dh) [q heads | k heads | v heads], cos / sin (S, Dh), d_out
+    (S, H*Dh), all values of `dt`.  q and k are rotated with rope_ref (the kernel's rotation is bma_rope2's, bit for
+    bit), attention_ref runs on the rotated operands, and dq' / dk' with their tolerances go back through the inverse
+    rotation g_d = cos_d g'_d -+ sin_d g'_p (p the partner 64 away) exactly:
+    tol_d = |cos_d| tol'_d + |sin_d| tol'_p + 3u (|cos_d g'_d| + |sin_d g'_p|) + 2 eta -- the kernel rounds dq' / dk' to
+    `dt` first (that rounding is already in tol'), then the two products (relative u each, or half a subnormal spacing
+    eta: without that floor a correct fp16 evaluation reaches 1.38 on a dk of order 1e-6, whatever C) and their sum.  o (S, H*Dh), lse (H, S) natural
+    log, dqkv (S, 3*H*Dh) and the tolerances of o and dqkv, in the kernel's layouts."""
+    S, Dh = qkv.shape[0], cos.shape[-1]
+    q, k, v = (t.reshape(S, H, Dh) for t in f64(qkv).split(H * Dh, dim=-1))
+    c, s = f64(cos).reshape(1, S, Dh), f64(sin).reshape(1, S, Dh)
+    rot = lambda t, sign: rope_ref(t.transpose(0, 1)[None], c, s, sign, dt)[0].transpose(0, 1)      # noqa: E731
+    ref = attention_ref(rot(q, 1.0), rot(k, 1.0), v, f64(d_out).reshape(S, H, Dh), scale, True, dt)
+    u, eta = unit_roundoff(dt), half_subnormal(dt)
+    cc, ss = c[0][:, None], s[0][:, None]                                   # (S, 1, Dh)
+    sign = torch.cat([torch.ones(Dh // 2), -torch.ones(Dh // 2)]).to(cc)    # -(rotate_half's sign)
+    grads, tols = [], []
+    for name in ("dq", "dk"):
+        g, t = getattr(ref, name), attention_tol(ref, name, dt)
+        gp, tp = _rot_partner(g), _rot_partner(t)
+        grads.append(cc * g + sign * ss * gp)
+        tols.append(cc.abs() * t + ss.abs() * tp + 3.0 * u * ((cc * g).abs() + (ss * gp).abs()) + 2.0 * eta)
+    grads.append(ref.dv)
+    tols.append(attention_tol(ref, "dv", dt))
+    flat = lambda ts: torch.cat([t.reshape(S, H * Dh) for t in ts], -1)      # noqa: E731
+    return B1Ref(ref.o.reshape(S, H * Dh), ref.lse2 / LOG2E, flat(grads), attention_tol(ref, "o", dt).reshape(S, H * Dh), flat(tols))
+
+
+def b1_attention_ratios(got, ref: B1Ref):
+    """{name: (worst error / bound, element)} for `o` (row, column), `lse` (head, row) and `dqkv` (row, column: q heads |
+    k heads | v heads) of the dict `got`."""
+    tol = {"o": ref.tol_o, "dqkv": ref.tol_dqkv, "lse": lse_tol(ref.lse)}
+    out = {}
+    for name, g in got.items():
+        want = getattr(ref, name)
+        out[name] = _worst(torch.nan_to_num((f64(g).to(want.device) - want).abs(), nan=float("inf")), tol[name])
+    return out
+
+
+# ---- the cases both test files run ----
+# (Lq, Lk) at 128-wide heads, H = Hkv = 2, causal: one key (dq and dk exactly zero, the odd-chunk half idle); one query
+# behind a prefix; on and off the 16-row tile; around the 32-key chunk (33: a last chunk of one key, seen by one query);
+# around the 64-row workgroup (65: a second workgroup of one row on both sides); even and odd chunk counts (the halves
+# unequal); a prefix of exactly two chunks; diagonals that cross the chunks off their edges
+ATTN_SHAPES = [(1, 1), (1, 33), (16, 16), (17, 17), (31, 31), (32, 32), (33, 33), (64, 64), (65, 65), (97, 97), (129, 129),
+               (20, 84), (44, 107), (33, 98), (65, 200)]
+ATTN_FAMILIES = ["randn", "sharp", "slow climb", "fast climb", "falling", "late outlier", "v ramp"]
+AttnCase = namedtuple("AttnCase", "Lq Lk H Hkv Dh causal")
+ATTN_TWO_TILE_CASES = [AttnCase(130, 130, 2, 2, 72, True), AttnCase(128, 128, 2, 2, 72, True), AttnCase(128, 128, 2, 2, 72, False)]
+
+
+def attention_cases():
+    """Every (Lq, Lk, H, Hkv, Dh, causal) of the per-element tests: ATTN_SHAPES, then four shapes each at the other head
+    widths and for grouped heads, then every key visible."""
+    cases = [AttnCase(Lq, Lk, 2, 2, 128, True) for Lq, Lk in ATTN_SHAPES]
+    for Dh in (64, 72, 256):
+        cases += [AttnCase(Lq, Lk, 2, 2, Dh, True) for Lq, Lk in ((33, 33), (65, 65), (44, 107), (65, 200))]
+    for Hkv in (2, 1):
+        cases += [AttnCase(Lq, Lk, 4, Hkv, 128, True) for Lq, Lk in ((17, 17), (129, 129), (33, 98), (65, 200))]
+    cases += [AttnCase(Lq, Lk, 2, 2, 128, False) for Lq, Lk in ((33, 33), (65, 97), (100, 100))]
+    return cases
+
+
+B1_S = [1, 15, 16, 17, 31, 32, 33, 48, 65, 80]
+B1_H = [1, 3]
+
+
+def attention_inputs(case: AttnCase, dt, family, seed=0):
+    """(q, k, v, d_out) on the CPU in `dt`.  randn: all four standard normal.  sharp: q times 4 -- the softmax is sharp,
+    every row's output of order one, the dominant keys at random places in each row, so that a missing or leaked key
+    moves some row grossly.  The four ramps add a score that depends on the key alone, through dim 0 of k (q[.., 0] = 1,
+    0.25 on odd rows so that the lanes of one wave differ; the other dims small), in log2 units: +0.05 a key (the running
+    maximum creeps up: alpha != 1 on every chunk), +0.4 a key (it jumps), -0.3 a key (it never moves after the first
+    chunk: alpha == 1, and in fp16 far keys' P underflow), one key 40 above the rest near the end.  v ramp: randn with v
+    scaled per key by linspace(0.5, 2), so that a permuted key order inside a k-step shows."""
+    Lq, Lk, H, Hkv, Dh, _ = case
+    gen = torch.Generator().manual_seed(100003 * seed + 1009 * Lq + 31 * Lk + 7 * Dh + H + 3 * Hkv + ATTN_FAMILIES.index(family))
+    q, k, v, do = _randn((Lq, H, Dh), gen), _randn((Lk, Hkv, Dh), gen), _randn((Lk, Hkv, Dh), gen), _randn((Lq, H, Dh), gen)
+    if family == "sharp":
+        q = 4.0 * q
+    elif family == "v ramp":
+        v = v * torch.linspace(0.5, 2.0, Lk)[:, None, None]
+    elif family != "randn":
+        pos = torch.arange(Lk, dtype=torch.float32)
+        ramp = {"slow climb": 0.05 * pos, "fast climb": 0.4 * pos, "falling": -0.3 * pos,
+                "late outlier": 40.0 * (pos == (19 * Lk) // 20)}[family]
+        k = 0.05 * k
+        k[..., 0] = (ramp / (Dh ** -0.5 * LOG2E))[:, None]
+        q = 0.5 * q
+        q[..., 0] = 1.0
+        q[(Lk - Lq + 1) % 2::2, :, 0] = 0.25          # odd POSITIONS
+    return q.to(dt), k.to(dt), v.to(dt), do.to(dt)
+
+
+def b1_inputs(S, H, dt, family, seed=0):
+    """(qkv (S, 3*H*128) as a view of rows 64 elements wider, cos, sin (S, 128), d_out (S, H*128)) on the CPU in `dt`: the
+    q, k, v of attention_inputs laid out as the fused projection's output, angles uniform in [0, 2 pi)."""
+    q, k, v, do = attention_inputs(AttnCase(S, S, H, H, 128, True), dt, family, seed)
+    gen = torch.Generator().manual_seed(977 * seed + S + 131 * H)
+    ang = torch.rand((S, 64), generator=gen) * 6.28
+    emb = torch.cat([ang, ang], -1)
+    big = torch.zeros((S, 3 * H * 128 + 64), dtype=dt)
+    big[:, :3 * H * 128] = torch.cat([t.reshape(S, H * 128) for t in (q, k, v)], -1)
+    return big[:, :3 * H * 128], emb.cos().to(dt), emb.sin().to(dt), do.reshape(S, H * 128)

@@ -552,6 +552,9 @@ def test_tower_attention_64_wide_heads_every_key_visible(dtype):
         assert rel(out, o_ref.detach()) <= 3 * eps, (H, L, Dh, causal, rel(out, o_ref.detach()))
         for name, mine, want in (("dq", dq, gq), ("dk", dk, gk), ("dv", dv, gv)):
             assert rel(mine, want) <= 6 * eps, (name, H, L, Dh, causal, rel(mine, want))
+        if H * L * L <= 2 ** 24:                  # and every element against its own row's bound (oracle/kernels.py: attention_ref)
+            per = K.attention_ratios({"o": out, "dq": dq, "dk": dk, "dv": dv}, K.attention_ref(q, k, v, do, scale, causal, dtype), dtype)
+            assert all(r <= 1.0 for r, _ in per.values()), (H, L, Dh, causal, per)
         if L > 1:
             ql, kl, vl = (t.detach().clone().requires_grad_() for t in (q, k, v))
             ol = torch.nn.functional.scaled_dot_product_attention(ql.transpose(0, 1)[None], kl.transpose(0, 1)[None], vl.transpose(0, 1)[None],
@@ -638,6 +641,9 @@ def test_causal_attention_forward_and_backward_match_float64(dtype):
         assert rel(out, o_ref.detach()) <= 3 * eps, (H, Lq, Lk, rel(out, o_ref.detach()))
         for name, mine, want in (("dq", dq, gq), ("dk", dk, gk), ("dv", dv, gv)):
             assert rel(mine, want) <= 6 * eps, (name, H, Lq, Lk, rel(mine, want))
+        if H * Lq * Lk <= 2 ** 24:                # and every element against its own row's bound (oracle/kernels.py: attention_ref)
+            per = K.attention_ratios({"o": out, "lse2": lse2, "dq": dq, "dk": dk, "dv": dv}, K.attention_ref(q, k, v, do, scale, True, dtype), dtype)
+            assert all(r <= 1.0 for r, _ in per.values()), (H, Lq, Lk, per)
         if Lq == Lk and Lq > 1:
             ql, kl, vl = (t.detach().clone().requires_grad_() for t in (q, k, v))
             ol = torch.nn.functional.scaled_dot_product_attention(ql.transpose(0, 1)[None], kl.transpose(0, 1)[None], vl.transpose(0, 1)[None],
@@ -698,6 +704,9 @@ def test_causal_attention_grouped_queries_and_256_wide_heads(dtype):
         for name, mine, want in (("dq", dq, gq), ("dk", dk, gk), ("dv", dv, gv)):
             # (the group's sum is taken in fp32 before the one rounding: no worse than a single head's)
             assert rel(mine, want) <= 6 * eps, (name, case, rel(mine, want))
+        if H * Lq * Lk <= 2 ** 24:                # and every element against its own row's bound (oracle/kernels.py: attention_ref)
+            per = K.attention_ratios({"o": out, "lse2": lse2, "dq": dq, "dk": dk, "dv": dv}, K.attention_ref(q, k, v, do, scale, causal, dtype), dtype)
+            assert all(r <= 1.0 for r, _ in per.values()), (case, per)
         if Lq == Lk and Lq > 1:
             ql, kl, vl = (t.detach().clone().requires_grad_() for t in (q, k, v))
             ol = torch.nn.functional.scaled_dot_product_attention(
@@ -1107,6 +1116,9 @@ def test_b1_attention_forward_and_backward(dtype):
         gerr = (grad.float() - ref_grad.float()).abs().max() / ref_grad.abs().max()
         gnorm = (grad.float() - ref_grad.float()).norm() / ref_grad.float().norm()
         assert float(gerr) < 16 * eps and float(gnorm) < 4 * eps, (S, H, float(gerr), float(gnorm))
+        # and every element against its own bound (oracle/kernels.py: b1_attention_ref)
+        per = K.b1_attention_ratios({"o": out.detach(), "lse": lse, "dqkv": grad}, K.b1_attention_ref(qkv, cos, sin, H, scale, dout, dtype))
+        assert all(r <= 1.0 for r, _ in per.values()), (S, H, per)
         (grad2,) = torch.autograd.grad(ops.B1AttentionFn.apply(mine, cos, sin, H, scale), mine, dout)
         assert torch.equal(grad, grad2)
     # what it does not take
