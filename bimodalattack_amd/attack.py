@@ -302,6 +302,14 @@ class BimodalAttack:
         self._margin_kappa = float(self.opt.margin_kappa) if self.opt.loss_rule == "margin" else None
         if self._margin_kappa is not None:
             logger.info(f"Target loss: margin, kappa = {self._margin_kappa} (loss_rule; the default is the cross-entropy)")
+        # token_dist_weight > 0: the top-k ranks the token gradient plus that weight times the embedding distance to the current
+        # token (candidate_sampling); 0.0: the raw gradient, the kernel never runs
+        self._token_dist_weight = float(self.opt.token_dist_weight)
+        self._token_dist_eff = None            # the launch argument: float32(weight * emb_scale), set once the model is known
+        self._token_dist_buf = None            # the (n_opt, V) fp32 scores, one buffer for the run
+        if self._token_dist_weight > 0:
+            logger.info(f"Token top-k: gradient + {self._token_dist_weight} * embedding distance to the current token "
+                        f"(token_dist_weight; the default ranks the gradient alone)")
         if model.device.type != "cuda":
             raise RuntimeError(
                 f"bimodalattack_amd runs on an AMD GPU only (model is on {model.device}); there is no CPU path. "
@@ -310,6 +318,10 @@ class BimodalAttack:
         self.embedding_layer = self.hf.embedding
         self.not_allowed_ids = None if config.allow_non_ascii else get_nonascii_toks(tokenizer, device=model.device)
         self.mask_bits = ops.build_mask_bits(self.not_allowed_ids, self.embedding_layer.num_embeddings, model.device)
+        if self._token_dist_weight > 0:
+            # the distance is between the embeddings the model is fed (Gemma scales its table by sqrt(D)): ||s*a - s*b|| =
+            # s * ||a - b||, so the scale goes into the weight -- one multiplication in double, then one rounding
+            self._token_dist_eff = float(np.float32(self._token_dist_weight * float(self.hf.emb_scale)))
         self.stop_flag = False
         self.shard = CandidateSharder(enabled=self.opt.shard)
         self.emulate_world = EMULATE_WORLD             # (tools: rank 0's share of an N-rank run in one process)
@@ -731,7 +743,14 @@ class BimodalAttack:
         else:
             rnd, rank = self._draw(self._width(step), ids.numel())
             pos = ops.rand_positions(rnd, cfg.n_replace)
-        topk_idx = ops.mask_topk(g_tok[0], self.mask_bits, cfg.topk)
+        if self._token_dist_eff is not None:
+            buf = self._token_dist_buf
+            if buf is None or buf.shape != g_tok[0].shape or buf.device != g_tok.device:
+                buf = self._token_dist_buf = torch.empty(g_tok[0].shape, dtype=torch.float32, device=g_tok.device)
+            score = ops.token_dist_score(g_tok[0], self.embedding_layer.weight, ids, self._token_dist_eff, out=buf)
+            topk_idx = ops.mask_topk(score, self.mask_bits, cfg.topk)
+        else:
+            topk_idx = ops.mask_topk(g_tok[0], self.mask_bits, cfg.topk)
         sampled = ops.sample_scatter(ids, topk_idx, pos, rank)
         self.shard.sync_state(*([sampled] if image is None else [sampled, image]))
         self._last = dict(topk_idx=topk_idx, pos=pos, rank=rank, sampled=sampled)
@@ -1526,6 +1545,8 @@ class BimodalAttack:
             if st is not None:
                 st["sampled"] = self._last["sampled"].cpu().numpy()
                 st["topk_idx"] = self._last["topk_idx"].cpu().numpy()
+                if self._token_dist_eff is not None:
+                    st["token_dist_weight"] = self._token_dist_eff      # the launch argument (emb_scale folded in)
                 st["pos"] = self._last["pos"].cpu().numpy()
                 st["rank"] = self._last["rank"].cpu().numpy()
 

@@ -75,11 +75,14 @@ class EngineOptions:
     """Knobs of the MI355X engine that the reference has no field for: the ones a test or bench.py flips.
 
     Read from keyword arguments of :func:`bimodalattack_amd.run` or from the environment (``BMA_<NAME>``), never from
-    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule``, ``pgd_norm`` and ``loss_rule`` (with ``margin_kappa``) only changes speed (tests/test_attack_gpu.py runs the reference's golden
+    ``BimodalAttackConfig``.  Every one of them but ``pgd_rule``, ``pgd_norm``, ``loss_rule`` (with ``margin_kappa``) and ``token_dist_weight`` only changes speed (tests/test_attack_gpu.py runs the reference's golden
     trajectories with each restructuring off).  Finer switches that exist for A/B measurements only are module constants
     read from the environment once (round 5: 42 options -> 27): ``ops.OWN_KERNELS`` (each hand-written batch-1 kernel),
     ``attack.MASKLESS_B1_ATTENTION`` / ``CHUNK_QUANTUM`` / ``EMULATE_WORLD``, ``fused.FUSE_QK_ROPE``,
     ``hf_adapter.PAD_VISION_HEADS`` / ``FUSE_QUICK_GELU`` / ``FUSE_TOWER_QKV``.
+
+    ``token_dist_weight`` > 0 changes which tokens the sampling step may draw from, and with them the results: like the
+    rules above it is opt-in and never a default.
     """
 
     # "model": draw the sampling randoms on the model's device exactly where the reference draws them
@@ -203,18 +206,29 @@ class EngineOptions:
     # kappa of loss_rule="margin" (unread otherwise): a real number >= 0, +inf = no clamp.  A plain attribute like
     # loss_rule (keyword of run() / from_env, or BMA_MARGIN_KAPPA).
     margin_kappa = 0.0
+    # Weight w of the embedding-distance term of the token top-k (Faster-GCG's regulariser, the other half of the attack
+    # loss_rule="margin" comes from): candidate_sampling ranks g[i, v] + w * ||e(v) - e(x_i)||_2 instead of the raw one-hot
+    # gradient g, e() the embedding the model is fed (Gemma's table times sqrt(D)) -- the gradient is a first-order estimate
+    # at the current token x_i, and its error grows with that distance (csrc/token_dist.hip, contract in include/bma.h a3b:
+    # one more read of the embedding table per step).  A real number, finite and >= 0; 0.0 = off: the kernel never runs and
+    # sampling is today's path.  Only the top-k sets change -- the random positions and ranks, early_plan, gradient_ahead,
+    # the ragged plan and the multi-rank broadcast do not.  Changes results: opt-in, never a default.  A plain attribute like
+    # loss_rule (keyword of run() / from_env, or BMA_TOKEN_DIST_WEIGHT).
+    token_dist_weight = 0.0
 
     def __repr__(self) -> str:        # (the generated ones know the fields only)
         import dataclasses
         inner = ", ".join(f"{f.name}={getattr(self, f.name)!r}" for f in dataclasses.fields(self) if f.repr)
-        return f"{type(self).__name__}({inner}, loss_rule={self.loss_rule!r}, margin_kappa={self.margin_kappa!r})"
+        return f"{type(self).__name__}({inner}, loss_rule={self.loss_rule!r}, margin_kappa={self.margin_kappa!r}, " \
+               f"token_dist_weight={self.token_dist_weight!r})"
 
     def __eq__(self, other) -> bool:
         import dataclasses
         if other.__class__ is not self.__class__:
             return NotImplemented
         return all(getattr(self, f.name) == getattr(other, f.name) for f in dataclasses.fields(self)) \
-            and self.loss_rule == other.loss_rule and self.margin_kappa == other.margin_kappa
+            and self.loss_rule == other.loss_rule and self.margin_kappa == other.margin_kappa \
+            and self.token_dist_weight == other.token_dist_weight
 
     __hash__ = None
 
@@ -274,6 +288,12 @@ class EngineOptions:
                 opts.margin_kappa = float(env["BMA_MARGIN_KAPPA"])
             except ValueError:
                 raise ValueError(f"margin_kappa (BMA_MARGIN_KAPPA) must be a number >= 0, got {env['BMA_MARGIN_KAPPA']!r}") from None
+        if "BMA_TOKEN_DIST_WEIGHT" in env:
+            try:
+                opts.token_dist_weight = float(env["BMA_TOKEN_DIST_WEIGHT"])
+            except ValueError:
+                raise ValueError(f"token_dist_weight (BMA_TOKEN_DIST_WEIGHT) must be a finite number >= 0, "
+                                 f"got {env['BMA_TOKEN_DIST_WEIGHT']!r}") from None
         for k, v in overrides.items():
             if v is None:
                 continue
@@ -294,6 +314,10 @@ class EngineOptions:
         if isinstance(k, bool) or not isinstance(k, (int, float)) or not k >= 0:      # NaN fails the comparison
             raise ValueError(f"margin_kappa must be a real number >= 0 (+inf: no clamp), got {k!r}")
         opts.margin_kappa = float(k)
+        w = opts.token_dist_weight
+        if isinstance(w, bool) or not isinstance(w, (int, float)) or not 0 <= w < float("inf"):     # NaN fails the comparison
+            raise ValueError(f"token_dist_weight must be a finite real number >= 0 (0: off), got {w!r}")
+        opts.token_dist_weight = float(w)
         if opts.tp_gradient not in (False, True, "graph"):
             raise ValueError(f"tp_gradient must be False, True or 'graph', got {opts.tp_gradient!r}")
         return opts

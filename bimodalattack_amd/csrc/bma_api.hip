@@ -133,6 +133,7 @@ extern "C" const char* bma_profile_kernel_name(int kernel) {
     case BMA_K_MELLOWMAX_DLOGITS: return "mellowmax_dlogits_kernel";
     case BMA_K_MARGIN: return "margin_rows_kernel";
     case BMA_K_MARGIN_DLOGITS: return "margin_dlogits_kernel";
+    case BMA_K_TOKEN_DIST: return "token_dist_kernel";
     default: return "?";
   }
 }

@@ -63,6 +63,8 @@ PROTOTYPES = {
                                   c_void_p, c_void_p, c_void_p, c_float, c_void_p]),
     "bma_mask_topk_ws_bytes": (c_size_t, [c_int, c_int, c_int]),
     "bma_mask_topk": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "bma_token_dist_score": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p, c_float,
+                                     c_void_p, c_int64, c_void_p]),
     "bma_rand_positions": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "bma_sample_scatter": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                    c_void_p, c_void_p]),
@@ -145,7 +147,8 @@ KERNEL_IDS = {"linf": 0, "ce_rows": 1, "ce_dlogits": 2, "mask_topk": 3, "sample_
               "ce_rows_grad": 6, "rmsnorm": 7, "swiglu": 8, "rope": 9, "attn_merge": 10, "gather_rows": 11,
               "ragged_attn": 12, "prefix_attn": 13, "add_rmsnorm": 14, "gemm_nt": 15, "b1_attn": 16, "gemm_mid": 17, "causal_attn": 18,
               "apgd": 19, "l2": 20, "mellowmax": 21, "mellowmax_dlogits": 22,
-              "margin": 23, "margin_dlogits": 24}
+              "margin": 23, "margin_dlogits": 24,
+              "token_dist": 26}        # (25 stays empty: tests/test_margin.py pins it as the first unnamed slot)
 
 
 def profile_enable(on: bool) -> None:

@@ -373,6 +373,56 @@ def mask_topk(grad: torch.Tensor, mask_bits: Optional[torch.Tensor], k: int) -> 
     return out
 
 
+TOKEN_DIST_ROWS = 32            # suffix positions served by one pass over the table (BMA_TOKEN_DIST_ROWS)
+
+
+def token_dist_score(grad: torch.Tensor, emb: torch.Tensor, ids: torch.Tensor, weight: float,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grad[i, v] + weight * ||emb[v] - emb[ids[i]]||_2 as float32 (rows, V): the token gradient with the embedding-distance
+    term of EngineOptions.token_dist_weight, which `mask_topk` then ranks (include/bma.h, a3b).
+
+    grad (rows, V) and emb (V, D) in float32, bfloat16 or float16, independently; ids (rows,) int64; weight finite and >= 0.
+    The table must start on a 16-byte boundary with rows of a multiple of 16 bytes, 16 bytes apart at least (an embedding
+    weight does).  `out`: a float32 (rows, V) tensor with a contiguous last dimension to take the result.  Launches recorded
+    under the "token_dist" profile slot."""
+    if grad.dim() != 2:
+        raise ValueError("grad must be (rows, V)")
+    if emb.dim() != 2:
+        raise ValueError("emb must be (V, D)")
+    dev = _need_gpu(grad, emb, ids)
+    rows, V = grad.shape
+    D = emb.shape[1]
+    if emb.shape[0] != V:
+        raise ValueError(f"emb has {emb.shape[0]} rows, grad {V} columns")
+    if ids.dtype != torch.int64 or ids.dim() != 1 or ids.numel() != rows or not ids.is_contiguous():
+        raise ValueError("ids must be `rows` contiguous int64 values")
+    if rows < 1 or V < 1 or D < 1:
+        raise ValueError("token_dist_score needs at least one row, one token and one column")
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)):
+        raise ValueError(f"token_dist weight must be a real number, got {weight!r}")
+    weight = float(weight)
+    if not (weight >= 0.0 and weight != float("inf")):
+        raise ValueError(f"token_dist weight must be finite and >= 0, got {weight!r}")
+    gdt, edt = _dt(grad), _dt(emb)
+    if grad.stride(1) != 1 or grad.stride(0) < V:
+        grad = grad.contiguous()
+    es = emb.element_size()
+    if emb.stride(1) != 1 or emb.stride(0) < D or (emb.stride(0) * es) % 16:
+        emb = emb.contiguous()
+    if emb.data_ptr() % 16:
+        emb = emb.clone(memory_format=torch.contiguous_format)          # (a fresh allocation starts on the grid)
+    if (D * es) % 16:
+        raise ValueError(f"token_dist_score: table rows of {D * es} bytes are not a multiple of 16")
+    if out is None:
+        out = torch.empty((rows, V), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.shape != (rows, V) or out.device != dev or out.stride(1) != 1 or out.stride(0) < V:
+        raise ValueError("bad out tensor")
+    check("bma_token_dist_score", lib.bma_token_dist_score(grad.data_ptr(), grad.stride(0), rows, V, gdt, emb.data_ptr(),
+                                                           emb.stride(0), D, edt, ids.data_ptr(), weight, out.data_ptr(),
+                                                           out.stride(0), _stream(dev)))
+    return out
+
+
 def rand_positions(rnd: torch.Tensor, n_replace: int) -> torch.Tensor:
     """argsort(rnd)[..., :n_replace] -- reference :150-154."""
     dev = _need_gpu(rnd)

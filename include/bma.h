@@ -242,6 +242,55 @@ int bma_mask_topk(const void* grad, int64_t ld_row, int rows, int V, int dtype,
                   const uint32_t* mask_bits, int k, int64_t* idx_out, void* ws, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * a3b  the embedding-distance term of the token top-k (opt-in,
+ *      EngineOptions.token_dist_weight > 0; the reference has no such term, this is
+ *      the engine's own contract: Faster-GCG's distance regulariser on the token
+ *      gradient, whose first-order error grows with the distance of a replacement's
+ *      embedding from the current one)
+ *   out[i*ld_out + v] = f32(grad[i, v]) + weight * sqrt( sum_c (E[v, c] - E[ids[i], c])^2 )
+ * for i < rows, v < V: what bma_mask_topk (BMA_F32) then ranks in place of grad.
+ * grad: rows x V of `gdtype`, row i at grad + i*ld_row (elements), as bma_mask_topk's.
+ * emb:  the table, V x D of `edtype`, row v at emb + v*ld_emb (elements).
+ * ids:  rows int64 current tokens.     out: rows x V fp32, row i at out + i*ld_out.
+ * Arithmetic form: the DIFFERENCE form, in fp32, on the table's elements converted
+ *   exactly to fp32 -- never ||a||^2 + ||b||^2 - 2 a.b, which cancels.  sqrtf is
+ *   correctly rounded (the build has no fast-math); the order of summation over c is
+ *   free and so is FMA contraction (of the squares into the sum, of weight * d into
+ *   the add).  Per element the result lies within
+ *       2^-24 * ((D/2 + 4) * weight * d + 2 * |s|)
+ *   of the exact value s = g + weight * d: at most D + 2 roundings on the sum of
+ *   squares, halved by the square root, one each for the root, the product, the add.
+ * Exact cases: out[i, ids[i]], and out[i, v] for any v whose table row equals row
+ *   ids[i] bit for bit, is f32(grad[i, v]) bit for bit where those rows are finite
+ *   (the sum is +0 exactly; a gradient of -0.0 comes out +0.0, as IEEE gives
+ *   g + 0.0; an inf in both rows is inf - inf = NaN like anywhere else).  weight == 0 is allowed
+ *   and follows IEEE arithmetic like any other: 0 * inf = NaN.
+ * Special values: NaN and inf in grad or emb propagate as IEEE arithmetic gives
+ *   them (inf - inf = NaN in a difference; bma_mask_topk ranks NaN first).  An
+ *   ids[i] outside [0, V) cannot be seen by the host without a synchronisation: it
+ *   is never read through, row i of out is all NaN, the other rows are written
+ *   normally.
+ * Arguments, checked in this order: rows, V, D >= 1, ld_row >= V, ld_out >= V,
+ *   ld_emb >= D (BMA_EINVAL); weight finite and >= 0 (BMA_EINVAL); gdtype and edtype
+ *   each any of f32 / bf16 / f16, independently (BMA_EDTYPE); no null pointer
+ *   (BMA_EINVAL); rows <= 65535 * BMA_TOKEN_DIST_ROWS (BMA_ELIMIT); emb 16-byte
+ *   aligned with D*elem and ld_emb*elem multiples of 16 (bma_splice's rule), grad and
+ *   out element-aligned, ids 8-byte aligned (BMA_EALIGN).
+ * Side effects: grad and emb are not modified; every element of out[0:rows, 0:V] is
+ *   written by exactly one lane, nothing else is written.  One launch; no
+ *   allocation, no synchronisation: capturable into a hipGraph.
+ * Table reads: the table is read from HBM once per group of BMA_TOKEN_DIST_ROWS = 32
+ *   rows, in coalesced 16-byte loads (a 20-token suffix costs one read: 263 MB for
+ *   LLaVA's 32064 x 4096 bf16); the current rows are re-read per 64 table rows,
+ *   from L2.
+ * ------------------------------------------------------------------------- */
+#define BMA_TOKEN_DIST_ROWS 32
+int bma_token_dist_score(const void* grad, int64_t ld_row, int rows, int V, int gdtype,
+                         const void* emb, int64_t ld_emb, int D, int edtype,
+                         const int64_t* ids, float weight,
+                         float* out, int64_t ld_out, void* stream);
+
+/* ---------------------------------------------------------------------------
  * a3  sample_ids_from_grad, second half  (:150-162)
  * bma_rand_positions: pos[b, 0:n_rep] = the n_rep positions of row b of `rnd`
  *   (B x n_opt uniform floats) with the smallest values, in ascending order of
@@ -575,7 +624,9 @@ enum {
   BMA_K_RAGGED_ATTN = 12, BMA_K_PREFIX_ATTN = 13, BMA_K_ADD_RMSNORM = 14, BMA_K_GEMM_NT = 15, BMA_K_B1_ATTN = 16, BMA_K_GEMM_MID = 17, BMA_K_CAUSAL_ATTN = 18, BMA_K_APGD = 19, BMA_K_L2 = 20 /* every pass of bma_l2_step / bma_apgd_l2_step */,
   BMA_K_MELLOWMAX = 21 /* the loss pass of bma_mellowmax_target */, BMA_K_MELLOWMAX_DLOGITS = 22 /* its dlogits pass */,
   BMA_K_MARGIN = 23 /* the row pass of bma_margin_target */, BMA_K_MARGIN_DLOGITS = 24 /* its dlogits pass */,
-  BMA_K_COUNT = 25
+  /* 25 is left unnamed and unused: tests/test_margin.py pins bma_profile_kernel_name(25) == "?" */
+  BMA_K_TOKEN_DIST = 26 /* bma_token_dist_score */,
+  BMA_K_COUNT = 27
 };
 int bma_profile_enable(int on);
 int bma_profile_read(int kernel, int64_t* launches, double* total_ms, double* total_bytes);

@@ -58,6 +58,15 @@ def cases():
         out = torch.empty_like(x) if grad else None
         return lambda: ops.margin_target(x, lab, 0.0, want_match=True, want_dlogits=grad, out=out)
 
+    def token_dist(n_opt, V, D):
+        # one pass over the whole table (V * D * 2 bytes) for up to 32 positions; the gradient in and the fp32 score out are
+        # n_opt * V * 6 bytes beside it.  Also FMA-bound: n_opt * V * D subtract + FMA pairs on the fp32 vector pipe
+        table = (torch.randn((V, D), generator=g, device=DEV) * 0.02).to(bf)
+        grad = (torch.randn((n_opt, V), generator=g, device=DEV) * 0.01).to(bf)
+        ids = torch.randint(0, V, (n_opt,), generator=g, device=DEV)
+        out = torch.empty((n_opt, V), dtype=torch.float32, device=DEV)
+        return lambda: ops.token_dist_score(grad, table, ids, 0.1, out=out)
+
     def splice(B, lens, D, V=32064, n_opt=19):
         table = torch.randn((V, D), generator=g, device=DEV).to(bf)
         ids = torch.randint(0, V, (B, n_opt), generator=g, device=DEV)
@@ -331,6 +340,8 @@ def cases():
         "margin/loss_B512_T20_V32064": ("margin", lambda: margin(512, 20, 32064, False)),
         "margin/dlogits_B512_T20_V32064": ("margin_dlogits", lambda: margin(512, 20, 32064, True)),
         "margin/loss_B128_T20_V262208": ("margin", lambda: margin(128, 20, 262208, False)),
+        "token_dist/llava_n20_V32064_D4096": ("token_dist", lambda: token_dist(20, 32064, 4096)),
+        "token_dist/gemma_n20_V262208_D2560": ("token_dist", lambda: token_dist(20, 262208, 2560)),
         "splice/c3_tail_B512_S44_D4096": ("splice", lambda: splice(512, ["g", 6, 19], 4096)),
         "splice/c3_full_B512_S65_D4096": ("splice", lambda: splice(512, [21, "g", 6, 19], 4096)),
         "splice/c4_full_B64_S643_D4096": ("splice", lambda: splice(64, [5, 576, 18, "g", 6, 19], 4096)),
