@@ -41,12 +41,13 @@ import torch
 from torch import Tensor
 
 from . import ops
-from .config import BimodalAttackConfig, BimodalAttackResult, EngineOptions, mellowmax_alpha
+from .config import BimodalAttackConfig, BimodalAttackResult, EngineOptions
 from .dist import CandidateSharder
 from .fused import DeferredNormMissed, FusedInference
 from . import gemm_tuning
 from .hf_adapter import HFAdapter
 from .pgd import ImageUpdate
+from .target_loss import TargetLoss
 from .layout import expected_row_counts, ragged_plan, ragged_rows, dynamic_width, segment_order, split_at_suffix, unique_rows
 from .utils import INIT_CHARS, FilterJob, get_nonascii_toks, is_oom, plan_chunk
 
@@ -294,14 +295,7 @@ class BimodalAttack:
         self.model, self.tokenizer, self.processor = model, tokenizer, processor
         self.config, self.normalize = config, normalize
         self.opt = options or EngineOptions.from_env()
-        # loss_rule "mellowmax": the one rule that reads config.mellowmax_alpha (checked here, when the rule is selected)
-        self._mm_alpha = mellowmax_alpha(config) if self.opt.loss_rule == "mellowmax" else None
-        if self._mm_alpha is not None:
-            logger.info(f"Target loss: mellowmax, alpha = {self._mm_alpha} (loss_rule; the default is the cross-entropy)")
-        # loss_rule "margin": kappa comes with the options (checked by from_env)
-        self._margin_kappa = float(self.opt.margin_kappa) if self.opt.loss_rule == "margin" else None
-        if self._margin_kappa is not None:
-            logger.info(f"Target loss: margin, kappa = {self._margin_kappa} (loss_rule; the default is the cross-entropy)")
+        self.target_loss = TargetLoss(config, self.opt)     # EngineOptions.loss_rule; its labels come with the prompt
         # token_dist_weight > 0: the top-k ranks the token gradient plus that weight times the embedding distance to the current
         # token (candidate_sampling); 0.0: the raw gradient, the kernel never runs
         self._token_dist_weight = float(self.opt.token_dist_weight)
@@ -454,7 +448,7 @@ class BimodalAttack:
             ids["after"] = self._encode(after, False)
         ids["target"] = self._encode(target, False)
         self.target_ids = ids["target"]
-        self.labels = self.target_ids[0].contiguous()
+        self.labels = self.target_loss.labels = self.target_ids[0].contiguous()
         self.T = int(self.labels.numel())
         with torch.no_grad():
             self.seg: Dict[str, Tensor] = {k: self.embedding_layer(v).detach() for k, v in ids.items()}
@@ -585,25 +579,15 @@ class BimodalAttack:
             self._gp_flag = bool(ok and hf.shared_prefix_configs())
         return self._gp_flag
 
-    def _target_loss(self, logits: Tensor, scoring: bool = False):
-        """The target loss by EngineOptions.loss_rule.  Gradient pass: the (T, V) target rows of the one sequence -> the scalar
-        loss, differentiable (the kernel's own dlogits).  scoring=True: (B, T, V) -> (loss (B,) fp32, early-stop hit or
-        None); the hit is the argmax test of the cross-entropy kernel's row pass under "ce" and "mellowmax"; the margin's
-        own row pass finds each row's top-1 and returns the same test from its one read of the logits."""
-        mm, want_hit = self._mm_alpha is not None, bool(scoring and self.config.early_stop)
-        if self._margin_kappa is not None:
-            if not scoring:
-                return ops.TargetMargin.apply(logits, self.labels, self._margin_kappa)
-            loss, hit, _, _ = ops.margin_target(logits, self.labels, self._margin_kappa, want_match=want_hit)
-            return loss, hit
-        if not scoring:
-            return (ops.TargetMellowmax.apply(logits, self.labels, self._mm_alpha) if mm
-                    else ops.TargetCrossEntropy.apply(logits, self.labels))
-        if mm:
-            hit = ops.ce_target(logits, self.labels, want_match=True)[1] if want_hit else None
-            return ops.mellowmax_target(logits, self.labels, self._mm_alpha)[0], hit
-        loss, hit, _, _ = ops.ce_target(logits, self.labels, want_match=want_hit)
-        return loss, hit
+    @property
+    def _mm_alpha(self) -> Optional[float]:
+        """alpha of loss_rule "mellowmax", None under any other rule."""
+        return self.target_loss.param if self.target_loss.rule == "mellowmax" else None
+
+    @property
+    def _margin_kappa(self) -> Optional[float]:
+        """kappa of loss_rule "margin", None under any other rule."""
+        return self.target_loss.param if self.target_loss.rule == "margin" else None
 
     def _gradient_eager(self, optim_ids: Tensor, image: Optional[Tensor] = None):
         """One forward/backward at batch 1.  The one-hot is never built: its gradient is
@@ -625,7 +609,7 @@ class BimodalAttack:
                 logits = self.hf.target_logits(x[:, :-1], self.T, rows_only=True)
             else:
                 logits = self.hf.target_logits(x, self.T, rows_only=False)
-        loss = self._target_loss(logits[0])
+        loss = self.target_loss.grad(logits[0])
         wanted = ([emb] if cfg.gcg_attack else []) + ([image] if cfg.pgd_attack else [])
         grads = list(torch.autograd.grad(loss, wanted))
         g_tok = None
@@ -971,7 +955,7 @@ class BimodalAttack:
             # the row list straight from the segments and the table: the padded (blocks, L, D) block is never built
             rows = ops.splice(segs, blocks, E, maps.ids, hf.emb_scale, rows=maps.flat).unsqueeze(0)
             logits = hf.target_logits_ragged(rows, self.T, cache, maps)
-            loss, hit = self._target_loss(logits, scoring=True)
+            loss, hit = self.target_loss.score(logits, bool(self.config.early_stop))
             return loss, hit
 
         if real is not None:
@@ -1167,7 +1151,7 @@ class BimodalAttack:
                 if scored is not None:
                     loss, hit = scored
                 else:
-                    loss, hit = self._target_loss(logits, scoring=True)
+                    loss, hit = self.target_loss.score(logits, bool(self.config.early_stop))
                 if self.score_log is not None and logits is not None:
                     self.score_log.append(dict(chunk_at=s, b=b, logits_bad=(~torch.isfinite(logits.float())).sum(),
                                                    x_bad=None if x is None else (~torch.isfinite(x.float())).sum()))
@@ -1844,7 +1828,7 @@ class _GradPrefix:
         tail = torch.cat([emb, a.seg["after"], a.seg["target_in"]], dim=1)
         with torch.enable_grad(), a.fused:
             logits = a.hf.target_logits_behind_grad_prefix(tail, a.T, self.rec)
-            loss = a._target_loss(logits[0])
+            loss = a.target_loss.grad(logits[0])
         g_emb, g_img = torch.autograd.grad(loss, [emb, self.image])
         with torch.no_grad():
             g_tok = (g_emb[0] @ E.t()).unsqueeze(0)
@@ -1889,7 +1873,7 @@ class _GradPrefix:
         tail = torch.cat([emb, a.seg["after"], a.seg["target_in"]], dim=1)
         with torch.enable_grad(), a.fused:
             logits = a.hf.target_logits_behind_grad_prefix(tail, a.T, self._cache)
-            loss = a._target_loss(logits[0])
+            loss = a.target_loss.grad(logits[0])
         (g_emb,) = torch.autograd.grad(loss, [emb])
         with torch.no_grad():
             g_tok = (g_emb[0] @ E.t()).unsqueeze(0)

@@ -192,14 +192,14 @@ class EngineOptions:
     pgd_norm: str = "linf"
     # The target loss of every scoring forward and gradient pass: "ce" = the reference's mean cross-entropy over the target
     # rows; "mellowmax" = nanoGCG's objective, the reference's own `mellowmax` (utils.py:35-36, shipped and never called)
-    # over the negated raw target logits with alpha = config.mellowmax_alpha (csrc/mellowmax_target.hip, contract in
+    # over the negated raw target logits with alpha = config.mellowmax_alpha (csrc/target_loss.hip, contract in
     # include/bma.h; losses may be negative).  Changes results like pgd_rule: opt-in, never a default.
     # `config.use_mellowmax` does NOT select it: the dataclass behaves as the reference's, which ignores that field.
     # (Set like every option -- keyword of run() / from_env, or BMA_LOSS_RULE -- but a plain attribute, not a dataclass
     # field: the field list is capped at 30, and this is the 31st option.)
     # "margin" = the Carlini-Wagner margin of the adversarial-robustness literature (Faster-GCG's loss, auto-PGD's
     # companion): per target row the best wrong logit minus the target logit, clamped below at -margin_kappa, averaged
-    # over the rows (csrc/margin_target.hip, contract in include/bma.h a2c).  A row whose margin is below -kappa is won
+    # over the rows (csrc/target_loss.hip, contract in include/bma.h a2c).  A row whose margin is below -kappa is won
     # and stops pulling; with kappa = 0 every margin < 0 means the early-stop test holds.  The same read of the logits
     # gives early_stop's argmax test, so the rule never runs the cross-entropy kernel.
     loss_rule = "ce"

@@ -59,6 +59,35 @@ __device__ __forceinline__ uint32_t pack16(float lo, float hi) {
 template <int DT>
 struct elem_bytes { static constexpr int value = (DT == BMA_F32) ? 4 : 2; };
 
+// element `i` of an array of `DT`, widened to fp32
+template <int DT>
+__device__ __forceinline__ float load_elem(const void* base, int64_t i) {
+  if (DT == BMA_F32) return static_cast<const float*>(base)[i];
+  const uint32_t h = static_cast<const uint16_t*>(base)[i];
+  return DT == BMA_BF16 ? bf16_bits_to_f32(h) : f16_bits_to_f32(h);
+}
+
+// `v` rounded to `DT`, as the low bits of a word
+template <int DT>
+__device__ __forceinline__ uint32_t elem_bits(float v) {
+  if (DT == BMA_F32) return __float_as_uint(v);
+  return DT == BMA_BF16 ? f32_to_bf16_bits(v) : f32_to_f16_bits(v);
+}
+
+// the 16 / elem_bytes elements of a 16-byte vector, widened to fp32
+template <int DT>
+__device__ __forceinline__ void unpack(const uint4_t& w, float* f) {
+  if (DT == BMA_F32) {
+    f[0] = __uint_as_float(w.x); f[1] = __uint_as_float(w.y);
+    f[2] = __uint_as_float(w.z); f[3] = __uint_as_float(w.w);
+  } else {
+    f[0] = unpack16<DT>(w.x, 0); f[1] = unpack16<DT>(w.x, 1);
+    f[2] = unpack16<DT>(w.y, 0); f[3] = unpack16<DT>(w.y, 1);
+    f[4] = unpack16<DT>(w.z, 0); f[5] = unpack16<DT>(w.z, 1);
+    f[6] = unpack16<DT>(w.w, 0); f[7] = unpack16<DT>(w.w, 1);
+  }
+}
+
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, BMA_WAVE));

@@ -160,6 +160,51 @@ def __getattr__(name: str):       # ApgdState lives in pgd.py, which imports thi
 
 
 # ---------------------------------------------------------------------------
+class _TargetOperands:
+    """What the three target losses share: the checked operands ((B,T,V) logits in the model dtype, last dim contiguous --
+    a strided view of a bigger tensor is fine; labels (T,) int64), the outputs and scratch of entry point `name`, and the
+    arguments before and after the rule's own.  `bad`: what is wrong with the rule's own parameter, if anything; it is
+    raised in its place among the checks, before `out` is looked at and before anything is allocated."""
+
+    def __init__(self, name: str, logits: torch.Tensor, labels: torch.Tensor, want_match: bool, want_dlogits: bool,
+                 grad_scale: float, out: Optional[torch.Tensor] = None, bad: Optional[str] = None):
+        if logits.dim() != 3:
+            raise ValueError("logits must be (B,T,V)")
+        dev = _need_gpu(logits, labels)
+        B, T, V = logits.shape
+        if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous():
+            raise ValueError("labels must be T contiguous int64 values")
+        if bad:
+            raise ValueError(bad)
+        if out is not None:
+            if not want_dlogits or out.shape != logits.shape or out.dtype != logits.dtype or out.device != dev or not out.is_contiguous():
+                raise ValueError("bad out tensor")
+        self.name, self.B, self.T, self.V = name, B, T, V
+        self.ws = torch.empty(getattr(lib, name + "_ws_bytes")(B, T) // 4, dtype=torch.float32, device=dev)
+        self.loss = torch.empty(B, dtype=torch.float32, device=dev)
+        self.match = torch.empty(B, dtype=torch.int32, device=dev) if want_match else None
+        self.dlog = None
+        if want_dlogits:
+            self.dlog = out if out is not None else torch.empty((B, T, V), dtype=logits.dtype, device=dev)
+        self.match_ptr = self.match.data_ptr() if want_match else None
+        if B:
+            if logits.stride(2) != 1 or logits.stride(1) < V or (B > 1 and logits.stride(0) < 0):
+                logits = logits.contiguous()
+            self._logits = logits         # the copy, if one was made, lives until the call has been enqueued
+            self._head = (logits.data_ptr(), logits.stride(0) if B > 1 else T * logits.stride(1), logits.stride(1),
+                          labels.data_ptr(), B, T, V, _dt(logits))
+            self._tail = (self.dlog.data_ptr() if want_dlogits else None, float(grad_scale), _stream(dev))
+
+    def call(self, *own) -> None:
+        """The launch, with the rule's own arguments between dtype and dlogits.  B == 0: nothing to do."""
+        if self.B:
+            check(self.name, getattr(lib, self.name)(*self._head, *own, *self._tail))
+
+    def result(self):
+        """(loss, match | None, dlogits | None, the first B*T words of ws as (B,T))."""
+        return self.loss, self.match, self.dlog, self.ws[: self.B * self.T].view(self.B, self.T)
+
+
 def ce_target(logits: torch.Tensor, labels: torch.Tensor, want_match: bool = False, want_dlogits: bool = False,
               grad_scale: float = 1.0):
     """Mean target cross-entropy per candidate.
@@ -168,48 +213,9 @@ def ce_target(logits: torch.Tensor, labels: torch.Tensor, want_match: bool = Fal
     bigger tensor is fine); labels (T,) int64.  Returns
     ``(loss fp32 (B,), match int32 (B,) | None, dlogits (B,T,V) | None, row_loss fp32 (B,T))``.
     """
-    if logits.dim() != 3:
-        raise ValueError("logits must be (B,T,V)")
-    dev = _need_gpu(logits, labels)
-    B, T, V = logits.shape
-    if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous():
-        raise ValueError("labels must be T contiguous int64 values")
-    if B == 0:
-        z = torch.empty(0, dtype=torch.float32, device=dev)
-        return z, (torch.empty(0, dtype=torch.int32, device=dev) if want_match else None), \
-            (torch.empty_like(logits) if want_dlogits else None), torch.empty(0, T, dtype=torch.float32, device=dev)
-    if logits.stride(2) != 1 or logits.stride(1) < V or (B > 1 and logits.stride(0) < 0):
-        logits = logits.contiguous()
-    ws = torch.empty(3 * B * T, dtype=torch.float32, device=dev)
-    assert ws.numel() * 4 == lib.bma_ce_target_ws_bytes(B, T)
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    match = torch.empty(B, dtype=torch.int32, device=dev) if want_match else None
-    dlog = torch.empty((B, T, V), dtype=logits.dtype, device=dev) if want_dlogits else None
-    check("bma_ce_target", lib.bma_ce_target(
-        logits.data_ptr(), logits.stride(0) if B > 1 else T * logits.stride(1), logits.stride(1), labels.data_ptr(),
-        B, T, V, _dt(logits), ws.data_ptr(), loss.data_ptr(), match.data_ptr() if want_match else None,
-        dlog.data_ptr() if want_dlogits else None, float(grad_scale), _stream(dev)))
-    return loss, match, dlog, ws[: B * T].view(B, T)
-
-
-class TargetCrossEntropy(torch.autograd.Function):
-    """mean CE over the target rows with the backward produced by the same kernel
-    launch sequence (the gradient pass, reference :1006-1028)."""
-
-    @staticmethod
-    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
-        x = logits.detach()
-        if x.dim() == 2:
-            x = x.unsqueeze(0)
-        loss, _, dlog, _ = ce_target(x, labels, want_dlogits=True)
-        ctx.save_for_backward(dlog)
-        ctx.in_shape = logits.shape
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        (dlog,) = ctx.saved_tensors
-        return (dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None
+    o = _TargetOperands("bma_ce_target", logits, labels, want_match, want_dlogits, grad_scale)
+    o.call(o.ws.data_ptr(), o.loss.data_ptr(), o.match_ptr)
+    return o.result()
 
 
 def mellowmax_target(logits: torch.Tensor, labels: torch.Tensor, alpha: float, want_dlogits: bool = False,
@@ -220,55 +226,11 @@ def mellowmax_target(logits: torch.Tensor, labels: torch.Tensor, alpha: float, w
     with no early-stop test (that stays ce_target's) and the softmax weights w in the place of the row losses.  `out`: a
     contiguous (B,T,V) tensor of the logits' dtype to take dlogits (any element-aligned start).
     """
-    if logits.dim() != 3:
-        raise ValueError("logits must be (B,T,V)")
-    dev = _need_gpu(logits, labels)
-    B, T, V = logits.shape
-    if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous():
-        raise ValueError("labels must be T contiguous int64 values")
     alpha = float(alpha)
-    if not (alpha > 0.0 and alpha != float("inf")):
-        raise ValueError(f"mellowmax alpha must be finite and > 0, got {alpha!r}")
-    if out is not None:
-        if not want_dlogits or out.shape != logits.shape or out.dtype != logits.dtype or out.device != dev or not out.is_contiguous():
-            raise ValueError("bad out tensor")
-    if B == 0:
-        z = torch.empty(0, dtype=torch.float32, device=dev)
-        return z, None, ((torch.empty_like(logits) if out is None else out) if want_dlogits else None), \
-            torch.empty(0, T, dtype=torch.float32, device=dev)
-    if logits.stride(2) != 1 or logits.stride(1) < V or (B > 1 and logits.stride(0) < 0):
-        logits = logits.contiguous()
-    w = torch.empty(B * T, dtype=torch.float32, device=dev)
-    assert w.numel() * 4 == lib.bma_mellowmax_target_ws_bytes(B, T)
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    dlog = None
-    if want_dlogits:
-        dlog = out if out is not None else torch.empty((B, T, V), dtype=logits.dtype, device=dev)
-    check("bma_mellowmax_target", lib.bma_mellowmax_target(
-        logits.data_ptr(), logits.stride(0) if B > 1 else T * logits.stride(1), logits.stride(1), labels.data_ptr(),
-        B, T, V, _dt(logits), alpha, w.data_ptr(), loss.data_ptr(), dlog.data_ptr() if want_dlogits else None,
-        float(grad_scale), _stream(dev)))
-    return loss, None, dlog, w.view(B, T)
-
-
-class TargetMellowmax(torch.autograd.Function):
-    """The mellowmax target loss of one sequence with the backward produced by the same call (the gradient pass under
-    loss_rule="mellowmax"): TargetCrossEntropy with the other rule."""
-
-    @staticmethod
-    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor, alpha: float) -> torch.Tensor:
-        x = logits.detach()
-        if x.dim() == 2:
-            x = x.unsqueeze(0)
-        loss, _, dlog, _ = mellowmax_target(x, labels, alpha, want_dlogits=True)
-        ctx.save_for_backward(dlog)
-        ctx.in_shape = logits.shape
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        (dlog,) = ctx.saved_tensors
-        return (dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None, None
+    bad = None if alpha > 0.0 and alpha != float("inf") else f"mellowmax alpha must be finite and > 0, got {alpha!r}"
+    o = _TargetOperands("bma_mellowmax_target", logits, labels, False, want_dlogits, grad_scale, out, bad)
+    o.call(alpha, o.ws.data_ptr(), o.loss.data_ptr())
+    return o.result()
 
 
 def margin_target(logits: torch.Tensor, labels: torch.Tensor, kappa: float, want_match: bool = False,
@@ -281,59 +243,60 @@ def margin_target(logits: torch.Tensor, labels: torch.Tensor, kappa: float, want
     test, from the same read of the logits.  `out`: a contiguous (B,T,V) tensor of the logits' dtype to take dlogits (any
     element-aligned start).
     """
-    if logits.dim() != 3:
-        raise ValueError("logits must be (B,T,V)")
-    dev = _need_gpu(logits, labels)
-    B, T, V = logits.shape
-    if labels.dtype != torch.int64 or labels.numel() != T or not labels.is_contiguous():
-        raise ValueError("labels must be T contiguous int64 values")
     kappa = float(kappa)
+    bad = None
     if not kappa >= 0.0:
-        raise ValueError(f"margin kappa must be >= 0 (+inf: no clamp), got {kappa!r}")
-    if V < 2:
-        raise ValueError("the margin needs V >= 2: there is no wrong logit")
-    if out is not None:
-        if not want_dlogits or out.shape != logits.shape or out.dtype != logits.dtype or out.device != dev or not out.is_contiguous():
-            raise ValueError("bad out tensor")
-    if B == 0:
-        z = torch.empty(0, dtype=torch.float32, device=dev)
-        return z, (torch.empty(0, dtype=torch.int32, device=dev) if want_match else None), \
-            ((torch.empty_like(logits) if out is None else out) if want_dlogits else None), \
-            torch.empty(0, T, dtype=torch.float32, device=dev)
-    if logits.stride(2) != 1 or logits.stride(1) < V or (B > 1 and logits.stride(0) < 0):
-        logits = logits.contiguous()
-    ws = torch.empty(3 * B * T, dtype=torch.float32, device=dev)
-    assert ws.numel() * 4 == lib.bma_margin_target_ws_bytes(B, T)
-    loss = torch.empty(B, dtype=torch.float32, device=dev)
-    match = torch.empty(B, dtype=torch.int32, device=dev) if want_match else None
-    dlog = None
-    if want_dlogits:
-        dlog = out if out is not None else torch.empty((B, T, V), dtype=logits.dtype, device=dev)
-    check("bma_margin_target", lib.bma_margin_target(
-        logits.data_ptr(), logits.stride(0) if B > 1 else T * logits.stride(1), logits.stride(1), labels.data_ptr(),
-        B, T, V, _dt(logits), kappa, ws.data_ptr(), loss.data_ptr(), match.data_ptr() if want_match else None,
-        dlog.data_ptr() if want_dlogits else None, float(grad_scale), _stream(dev)))
-    return loss, match, dlog, ws[: B * T].view(B, T)
+        bad = f"margin kappa must be >= 0 (+inf: no clamp), got {kappa!r}"
+    elif logits.dim() == 3 and logits.shape[2] < 2:
+        bad = "the margin needs V >= 2: there is no wrong logit"
+    o = _TargetOperands("bma_margin_target", logits, labels, want_match, want_dlogits, grad_scale, out, bad)
+    o.call(kappa, o.ws.data_ptr(), o.loss.data_ptr(), o.match_ptr)
+    return o.result()
 
 
-class TargetMargin(torch.autograd.Function):
-    """The margin target loss of one sequence with the backward produced by the same call (the gradient pass under
-    loss_rule="margin"): TargetCrossEntropy with the other rule."""
+class _TargetFunction(torch.autograd.Function):
+    """A target loss of one sequence ((T,V) or (1,T,V) logits) with the backward produced by the same kernel launch
+    sequence (the gradient pass, reference :1006-1028).  A rule's class has only its `forward`: which function above, and
+    the rule's parameter, if it has one, after the labels."""
 
     @staticmethod
-    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor, kappa: float) -> torch.Tensor:
+    def run(ctx, rule, logits: torch.Tensor, labels: torch.Tensor, *param) -> torch.Tensor:
         x = logits.detach()
         if x.dim() == 2:
             x = x.unsqueeze(0)
-        loss, _, dlog, _ = margin_target(x, labels, kappa, want_dlogits=True)
+        loss, _, dlog, _ = rule(x, labels, *param, want_dlogits=True)
         ctx.save_for_backward(dlog)
-        ctx.in_shape = logits.shape
+        ctx.in_shape, ctx.n_param = logits.shape, len(param)
         return loss[0]
 
     @staticmethod
     def backward(ctx, grad_out):
         (dlog,) = ctx.saved_tensors
-        return (dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None, None
+        return ((dlog * grad_out.to(dlog.dtype)).view(ctx.in_shape), None) + (None,) * ctx.n_param
+
+
+class TargetCrossEntropy(_TargetFunction):
+    """The mean cross-entropy over the target rows."""
+
+    @staticmethod
+    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        return _TargetFunction.run(ctx, ce_target, logits, labels)
+
+
+class TargetMellowmax(_TargetFunction):
+    """The mellowmax target loss (the gradient pass under loss_rule="mellowmax")."""
+
+    @staticmethod
+    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor, alpha: float) -> torch.Tensor:
+        return _TargetFunction.run(ctx, mellowmax_target, logits, labels, alpha)
+
+
+class TargetMargin(_TargetFunction):
+    """The margin target loss (the gradient pass under loss_rule="margin")."""
+
+    @staticmethod
+    def forward(ctx, logits: torch.Tensor, labels: torch.Tensor, kappa: float) -> torch.Tensor:
+        return _TargetFunction.run(ctx, margin_target, logits, labels, kappa)
 
 
 # ---------------------------------------------------------------------------

@@ -133,6 +133,9 @@ int bma_apgd_l2_step(const float* x, const float* g, const float* x0, float* pre
  *   ws        scratch of bma_ce_target_ws_bytes(B,T) bytes = 3*B*T 4-byte words,
  *                    left holding: [0,BT) per-row loss f32 (logsumexp - x[label]),
  *                    [BT,2BT) per-row argmax==label i32, [2BT,3BT) logsumexp f32
+ * Pointers element-aligned (logits, dlogits), 4-byte aligned (ws, loss, match)
+ * and 8-byte aligned (labels), else BMA_EALIGN; an unknown dtype is BMA_EDTYPE
+ * at B == 0 as well.
  * ------------------------------------------------------------------------- */
 size_t bma_ce_target_ws_bytes(int B, int T);
 int bma_ce_target(const void* logits, int64_t ld_cand, int64_t ld_row,

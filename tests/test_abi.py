@@ -66,6 +66,13 @@ def test_argument_validation_launches_nothing():
     assert lib.bma_ce_target(None, 0, 0, None, 1, 0, 10, 0, None, None, None, None, 1.0, None) == -1
     assert lib.bma_ce_target(16, 40, 10, 16, 4, 4, 10, 7, 16, 16, None, None, 1.0, None) == -2   # dtype
     assert lib.bma_ce_target(None, 0, 10, None, 0, 4, 10, 0, None, None, None, None, 1.0, None) == 0
+    assert lib.bma_ce_target(None, 0, 10, None, 0, 4, 10, 7, None, None, None, None, 1.0, None) == -2    # dtype, at B == 0 too
+    x, lab, ws, loss, mt, dl = 64, 128, 192, 256, 320, 384
+    for bad in (dict(x=x + 2), dict(ws=ws + 2), dict(loss=loss + 2), dict(mt=mt + 2), dict(lab=lab + 4), dict(dl=dl + 2)):
+        a = {**dict(x=x, lab=lab, ws=ws, loss=loss, mt=mt, dl=dl), **bad}                                  # misaligned pointer
+        assert lib.bma_ce_target(a["x"], 40, 10, a["lab"], 4, 4, 10, 0, a["ws"], a["loss"], a["mt"], a["dl"], 1.0, None) == -3
+    assert lib.bma_ce_target(x + 1, 40, 10, lab, 4, 4, 10, 1, ws, loss, None, None, 1.0, None) == -3    # logits off the element grid
+    assert lib.bma_ce_target(x, 40, 10, lab, 4, 4, 10, 2, ws, loss, None, dl + 1, 1.0, None) == -3      # dlogits off the element grid
     assert lib.bma_ce_target_ws_bytes(512, 20) == 3 * 512 * 20 * 4
     assert lib.bma_mask_topk(16, 100, 1, 100, 0, None, 101, 16, None, None) == -1   # k > V
     assert lib.bma_mask_topk(16, 5000, 1, 5000, 0, None, 4096, 16, None, None) == -5  # k > 2048
